@@ -21,12 +21,15 @@ refuses, unless ``--rehearsal`` (ranks then share devices round-robin and the
 line says so: ``"rehearsal": true``, ``n_gpus`` = distinct devices).  A gloo
 barrier + MAX of the per-rank elapsed times brackets the timed region.
 
-At N = 1 the line also carries the other BASELINE configs, each timed the same
-way in this process: ``c3`` (configs[2]: mixed resolution + iBOT masks),
-``fp8`` (configs[4]: E4M3 epilogue), ``c2_dri`` (C2 with restart markers,
-SURVEY §8(d)) and ``e2e`` (configs[4]: /dev/shm tar shards through
-``MI355XBackend.build_pipeline`` + ``build_pipeline_iterator``, the drop-in
-path), plus the CPU baseline.
+A plain run does only what the headline figure needs: synthesise and upload the
+set, warm up, time ``--steps`` steps, write the last timed step's outputs
+(``--dump-outputs DIR``) and print the line.  ``--full`` adds everything else:
+the serialized per-kernel pass with the roofline figures, and at N = 1 the
+other BASELINE configs, each timed the same way: ``c3`` (configs[2]: mixed
+resolution + iBOT masks), ``fp8`` (configs[4]: E4M3 epilogue), ``c2_dri`` (C2
+with restart markers), ``c2_prog`` and ``e2e`` (configs[4]:
+/dev/shm tar shards through ``MI355XBackend.build_pipeline`` +
+``build_pipeline_iterator``, the drop-in path), plus the CPU baseline.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md §Measurement for every field).
 """
@@ -395,11 +398,12 @@ def launch_ranks(n: int, argv: list[str], devices: int, rehearsal: bool = False,
 
 # ----------------------------------------------------------------------------- timing
 def run_leg(pipe, d_bytes, d_off, n_img: int, B: int, steps: int, warmup: int, world: int, dist,
-            maskgen=None, serial: bool = True) -> dict:
+            maskgen=None, serial: bool = True, sample=None) -> dict:
     """Time exactly ``steps`` device-resident batches (after ``warmup``), bracketed by a
     barrier + synchronize; then (``serial``) the same number of batches one at a time with
     the library's HIP-event timer (a kernel's events must not also span the other slots'
-    concurrently running kernels)."""
+    concurrently running kernels).  ``sample`` (``--dump-outputs``): called with what the
+    last timed step returned, after the timed region and before anything overwrites it."""
     import torch
     ccfg = pipe._cfg(*pipe._sizes())
     views = [sl.engine.alloc_views(ccfg, B) for sl in pipe._slots]  # one output set per in-flight slot
@@ -407,9 +411,10 @@ def run_leg(pipe, d_bytes, d_off, n_img: int, B: int, steps: int, warmup: int, w
 
     def step(k: int):
         s = (k % n_batches) * B
-        pipe.run_device_batch(d_bytes, d_off[s:s + B + 1], B, views=views[k % pipe.depth])
+        out = pipe.run_device_batch(d_bytes, d_off[s:s + B + 1], B, views=views[k % pipe.depth])
         if maskgen is not None:  # one mask per batch, broadcast to [B, H*W] (loader.py:585-590)
-            maskgen.generate(1).expand(B, -1)
+            return out, maskgen.generate(1).expand(B, -1)
+        return out, None
 
     # every batch's per-image status ([B, 4] int32 from the batch's own kernels) goes to a pinned
     # row asynchronously on the batch's stream, inside the timed region (an 8 KiB copy per
@@ -432,14 +437,17 @@ def run_leg(pipe, d_bytes, d_off, n_img: int, B: int, steps: int, warmup: int, w
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for k in range(steps):
-        step(warmup + k)
+        last = step(warmup + k)
         record_status(warmup + k)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
     out = {"dt": dt, "ktimes": {}, "t_ser": None, "last_batch": None}
+    if sample is not None and last is not None:
+        out["dumped"] = sample(*last)
     if serial:
         pipe.set_timing(True)
         pipe.kernel_times()
@@ -464,6 +472,33 @@ def run_leg(pipe, d_bytes, d_off, n_img: int, B: int, steps: int, warmup: int, w
     out["statuses_checked_total"] = int(rows * B)        # + warm-up + serialized pass
     out["recs"] = pipe.last_params()
     return out
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: bytes of float32 written at most (the views of a batch are ~1 GB)
+
+
+def dump_outputs(out_dir: Path, views: dict, mask, B: int) -> dict:
+    """``--dump-outputs``: what the last timed step returned, as ``<name>.npy`` in float32
+    (exact for bf16 / fp8): every view of a fixed, seeded subset of the batch's images (the
+    same rows of every view, whole images, as many as the budget holds) and, with masks on,
+    the batch's mask row.  The caller has synchronised the device."""
+    import torch
+    out_dir.mkdir(parents=True, exist_ok=True)
+    per_image = 4 * sum(v[0].numel() for v in views.values())
+    n = max(1, min(B, DUMP_BUDGET_BYTES // per_image))
+    rows = np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+    as_int = {1: torch.uint8, 2: torch.int16, 4: torch.int32}  # row gather on the bits: any output dtype
+    written = 0
+    for name, v in views.items():
+        idx = torch.from_numpy(rows).to(v.device)
+        a = v.view(as_int[v.element_size()]).index_select(0, idx).view(v.dtype).float().cpu().numpy()
+        np.save(out_dir / f"{name}.npy", a)
+        written += a.nbytes
+    if mask is not None:
+        a = mask[:1].float().cpu().numpy()
+        np.save(out_dir / "masks.npy", a)
+        written += a.nbytes
+    return {"images": int(n), "of_batch": int(B), "bytes": int(written)}
 
 
 def load_traffic(tag: str) -> tuple[dict, str | None]:
@@ -817,6 +852,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="allow more ranks than GPUs (round-robin sharing; the line is marked as a rehearsal)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher + rank aggregation only, no GPU work (CPU tests of the N-rank path)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the serialized per-kernel pass + roofline, and at "
+                         "N = 1 the c3 / fp8 / c2_dri / c2_prog / e2e legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned to DIR/<name>.npy (float32; a fixed seeded "
+                         "subset of the batch's images, every view of each; ranks > 1: DIR/rank<r>/)")
     ap.add_argument("--steps", type=int, default=98, help="timed steps (98 x 512 covers the 50k set once)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=512)
@@ -834,12 +875,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--masks", action="store_true", help="iBOT masks per batch (default with --mixed)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8", "fp32"])
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="time budget of each CPU-baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="N = 1: skip the c3 / fp8 / c2_dri / e2e legs (profiling runs)")
+                    help="--full at N = 1 without the c3 / fp8 / c2_dri / c2_prog / e2e legs")
     ap.add_argument("--extra-unique", type=int, default=1024, help="distinct encodes of the c3 / c2_dri legs")
     ap.add_argument("--h2d", action="store_true", help="also time the H2D-inclusive rate (pinned host bytes)")
-    ap.add_argument("--kernel-json", default="", help="write per-kernel times here (rank 0)")
+    ap.add_argument("--kernel-json", default="",
+                    help="write per-kernel times here (rank 0; runs the serialized per-kernel pass)")
     ap.add_argument("--e2e", action="store_true", help="C5 end-to-end leg even with --no-extras or N > 1")
     ap.add_argument("--gpu-queue", type=int, default=6, help="PipelineConfig.gpu_queue of the e2e leg")
     ap.add_argument("--shard-size", type=int, default=1000, help="samples per synthetic tar shard (e2e)")
@@ -993,7 +1035,8 @@ def dry_run(args, rank: int, world: int, local_rank: int) -> int:
 
 
 def run_rank(args, rank: int, world: int, local_rank: int) -> int:
-    extras = world == 1 and not args.no_extras
+    extras = args.full and world == 1 and not args.no_extras
+    serial = args.full or bool(args.kernel_json)  # the per-kernel pass: as many batches again, one at a time
     legs_on = set(args.legs.split(","))
     procs = _procs(args, world)
     # synthetic data first, before anything initialises the GPU in this process
@@ -1037,7 +1080,8 @@ def run_rank(args, rank: int, world: int, local_rank: int) -> int:
         mg.seed(rank_seed(1234, rank))
         return mg
 
-    def leg(u, n_img, mixed: bool, dtype: str, masks: bool, tag: str, steps: int, warmup: int, serial=True):
+    def leg(u, n_img, mixed: bool, dtype: str, masks: bool, tag: str, steps: int, warmup: int, serial=True,
+            sample=None):
         jp, hb, off, d_bytes, d_off = to_device(u, n_img)
         torch.cuda.synchronize()
         pipe = MI355XAugPipeline(None, cfg, B, seed=rank_seed(1234, rank), out_dtype=dtype, device=device,
@@ -1045,7 +1089,7 @@ def run_rank(args, rank: int, world: int, local_rank: int) -> int:
                                  workspace_bytes=B * (40 << 20) if mixed else 0)
         try:
             res = run_leg(pipe, d_bytes, d_off, n_img, B, steps, warmup, world, dist,
-                          maskgen=make_maskgen() if masks else None, serial=serial)
+                          maskgen=make_maskgen() if masks else None, serial=serial, sample=sample)
             ent_b = 0.0
             if res["last_batch"] is not None:
                 s_last = res["last_batch"]
@@ -1063,8 +1107,12 @@ def run_rank(args, rank: int, world: int, local_rank: int) -> int:
 
     masks_on = args.masks or args.mixed
     main_tag = "c3" if args.mixed else ("fp8" if args.dtype == "fp8" else ("dri" if args.restart_mcus else "c2"))
+    sample = None
+    if args.dump_outputs:
+        dump_dir = Path(args.dump_outputs) / f"rank{rank}" if world > 1 else Path(args.dump_outputs)
+        sample = lambda views, mask: dump_outputs(dump_dir, views, mask, B)  # noqa: E731
     res, summ, (pipe, host_buf, offsets) = leg(uniq, args.images, args.mixed, args.dtype, masks_on, main_tag,
-                                               args.steps, args.warmup)
+                                               args.steps, args.warmup, serial=serial, sample=sample)
     dt, per_rank = _rank_report(dist, world, rank, device, res["dt"], args.steps, B)
     distinct = check_distinct(per_rank, args.rehearsal)
 
@@ -1123,7 +1171,7 @@ def run_rank(args, rank: int, world: int, local_rank: int) -> int:
         e2e = run_leg_child(args, "e2e") if world == 1 else run_e2e(args, uniq, rank, world, cfg, B, dist)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         print("bench: cpu baseline", file=sys.stderr, flush=True)
         c1 = make_unique(256, 256, 256, 7, False, procs)
         cpu = cpu_baseline(uniq if not args.mixed else uniq[:256], c1, args.cpu_seconds)
@@ -1152,6 +1200,13 @@ def run_rank(args, rank: int, world: int, local_rank: int) -> int:
             "serialized_ms_per_step": summ.get("serialized_ms_per_step"),
             "cpu_baseline": cpu,
         }
+        if not serial:  # no per-kernel pass: the line carries no figure derived from it
+            for k in ("roofline", "roofline_kernels", "path_roofline", "kernels_ms_per_step", "serialized_ms_per_step"):
+                del line[k]
+        if not args.full:
+            del line["cpu_baseline"]
+        if "dumped" in res:
+            line["outputs_dumped"] = res["dumped"]
         if world > distinct:
             line["rehearsal"] = True
             line["note"] = f"{world} ranks shared {distinct} device(s): not a scaling measurement"

@@ -346,7 +346,7 @@ class ShmShardCache:
         self._pool = None
         self._in_flight: dict = {}
         self._warn_threshold = float(warn_threshold)
-        self._last_warn = 0.0
+        self._last_warn = float("-inf")  # never warned: time.monotonic() starts near 0 on a fresh boot
 
     @property
     def base(self) -> Path:

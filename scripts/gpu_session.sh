@@ -16,8 +16,9 @@ if has tests; then
   timeout -k 10 120 python -c 'import __graft_entry__ as g; g.smoke()' > gpurun_out/${TAG}_smoke.log 2>&1 || exit $?
 fi
 if has bench; then
-  timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || exit $?
-  head -c 300 gpurun_out/${TAG}_bench.json; echo
+  mkdir -p "${BENCH_OUT:=bench_out}"
+  timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $BENCH_OUT/${TAG}_bench.json 2> $BENCH_OUT/${TAG}_bench.err || exit $?
+  head -c 300 $BENCH_OUT/${TAG}_bench.json; echo
 fi
 if has prof; then
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_prof -o run --output-format csv -- \

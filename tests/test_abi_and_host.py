@@ -124,6 +124,44 @@ def test_shard_cache_lru(tmp_path):
     cache.close(remove=True)
 
 
+def test_shard_cache_warns_on_a_freshly_booted_host(tmp_path, monkeypatch):
+    """The first utilisation warning does not depend on the host's uptime: the monotonic
+    clock starts near zero at boot, and the once-a-minute limit applies from the first
+    warning on, not from the clock's origin."""
+    import time
+    import warnings
+
+    from dataloader_amd import tario
+    monkeypatch.setattr(time, "monotonic", lambda: 5.0)
+    cache = tario.ShmShardCache(job_id="boot", max_gb=100 / (1 << 30), warn_threshold=0.5, base_dir=tmp_path)
+    with pytest.warns(RuntimeWarning, match="utilisation"):
+        cache.put("/x/a.tar", b"a" * 60)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        cache.put("/x/a.tar", b"b" * 60)  # within the minute: silent
+    cache.close(remove=True)
+
+
+def test_bench_dump_outputs_is_a_fixed_sample(tmp_path):
+    """``bench.py --dump-outputs``: float32 files, the same seeded rows of every view, under the
+    byte budget, identical from call to call."""
+    import bench
+    B = 96
+    views = {"view_0": torch.randn(B, 3, 224, 224).bfloat16(), "view_1": torch.randn(B, 3, 96, 96).bfloat16()}
+    mask = torch.zeros(1, 256, dtype=torch.bool).expand(B, -1)
+    info = bench.dump_outputs(tmp_path / "a", views, mask, B)
+    bench.dump_outputs(tmp_path / "b", views, mask, B)
+    n = info["images"]
+    assert 1 <= n < B and info["bytes"] <= 64 << 20
+    rows = np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+    for name, v in views.items():
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (n, *v.shape[1:])
+        assert np.array_equal(a, v[torch.from_numpy(rows)].float().numpy())
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{name}.npy"))
+    assert np.load(tmp_path / "a" / "masks.npy").shape == (1, 256)
+
+
 def test_masking_generator_validation_matches_reference():
     from dataloader_amd.masking import MaskingGenerator
     with pytest.raises(ValueError):
