@@ -171,12 +171,21 @@ DHD int parse_jpeg(const uint8_t* p, int64_t len, int max_dim, ImgDesc* d, bool 
         d->restart_interval = rd16(s);
         break;
       case 0xE0:  // APP0: JFIF?
-        if (n >= 5 && s[0] == 'J' && s[1] == 'F' && s[2] == 'I' && s[3] == 'F' && s[4] == 0) saw_jfif = true;
+        if (n >= 4 && s[0] == 'J' && s[1] == 'F' && s[2] == 'I' && s[3] == 'F') {
+          // Pillow's APP handler reads the version at payload bytes 5..6 of anything that
+          // starts with "JFIF" and raises on a shorter one (the reference zero-fills)
+          if (n < 7) return (d->status = DINO_IMG_CORRUPT);
+          // jdmarker.c examine_app0: JFIF only with the whole 14-byte header (APP0_DATA_LEN)
+          if (n >= 14 && s[4] == 0) saw_jfif = true;
+        }
         break;
       case 0xEE:  // APP14: Adobe transform flag
-        if (n >= 12 && s[0] == 'A' && s[1] == 'd' && s[2] == 'o' && s[3] == 'b' && s[4] == 'e') {
-          saw_adobe = true;
-          adobe_transform = s[11];
+        if (n >= 5 && s[0] == 'A' && s[1] == 'd' && s[2] == 'o' && s[3] == 'b' && s[4] == 'e') {
+          if (n < 7) return (d->status = DINO_IMG_CORRUPT);  // Pillow reads the version at bytes 5..6
+          if (n >= 12) {  // examine_app14: APP14_DATA_LEN
+            saw_adobe = true;
+            adobe_transform = s[11];
+          }
         }
         break;
       case 0xDA: {  // SOS
@@ -272,11 +281,18 @@ have_scan:
   } else {
     d->mcus_x = ceil_div(d->width, 8 * mh);
     d->mcus_y = ceil_div(d->height, 8 * mv);
+    // libjpeg limits the blocks of an MCU per interleaved scan (per_scan_setup,
+    // JERR_BAD_MCU_SIZE), not per frame: the one scan of a kind-0 image holds every
+    // component; a kind-1 image is checked scan by scan (prog_walk) and never reads the
+    // frame's MCU table, which stays empty when the frame's blocks do not fit it
+    int frame_blocks = 0;
+    for (int c = 0; c < d->ncomp; ++c) frame_blocks += d->comp[c].h * d->comp[c].v;
+    const bool fits = frame_blocks <= kMaxBlocksPerMcu;
+    if (!fits && d->kind == 0) return (d->status = DINO_IMG_BADDATA);
     int b = 0;
     for (int c = 0; c < d->ncomp; ++c) {
       CompDesc& cd = d->comp[c];
-      if (b + cd.h * cd.v > kMaxBlocksPerMcu) return (d->status = DINO_IMG_BADDATA);
-      for (int y = 0; y < cd.v; ++y)
+      for (int y = 0; y < cd.v && fits; ++y)
         for (int x = 0; x < cd.h; ++x) {
           d->mcu_comp[b] = (uint8_t)c;
           d->mcu_bx[b] = (uint8_t)x;

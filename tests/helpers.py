@@ -59,13 +59,19 @@ def build_emu() -> ctypes.CDLL:
 
 def emu_decode(lib, jpeg: bytes, mode: int = 0, lanes: int = 1):
     from PIL import Image
-    try:
-        w, h = Image.open(io.BytesIO(jpeg)).size
-    except Exception:  # noqa: BLE001
-        w, h = 1, 1
+    buf = np.frombuffer(jpeg, np.uint8)
+    # the emulator writes width x height of its own parse (and nothing when that fails): a file
+    # that Pillow refuses but the parser accepts still gets a buffer of its real size
+    info = np.zeros(8, np.int32)
+    if lib.emu_parse(buf.ctypes.data_as(P), ctypes.c_int64(len(jpeg)), info.ctypes.data_as(P)) == 0:
+        w, h = int(info[1]), int(info[2])
+    else:
+        try:
+            w, h = Image.open(io.BytesIO(jpeg)).size
+        except Exception:  # noqa: BLE001
+            w, h = 1, 1
     out = np.zeros(h * w * 3, np.uint8)
     st = np.zeros(4, np.int32)
-    buf = np.frombuffer(jpeg, np.uint8)
     r = lib.emu_decode(buf.ctypes.data_as(P), ctypes.c_int64(len(jpeg)), mode, lanes,
                        out.ctypes.data_as(P), st.ctypes.data_as(P))
     return r, out.reshape(h, w, 3), st

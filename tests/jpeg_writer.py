@@ -132,14 +132,15 @@ class BitWriter:
         self.n = 0
 
     def bits(self, v: int, n: int):
-        for i in range(n - 1, -1, -1):
-            self.acc = (self.acc << 1) | ((v >> i) & 1)
-            self.n += 1
-            if self.n == 8:
-                self.out.append(self.acc)
-                if self.acc == 0xFF:
-                    self.out.append(0)
-                self.acc = self.n = 0
+        self.acc = (self.acc << n) | (v & ((1 << n) - 1))
+        self.n += n
+        while self.n >= 8:
+            self.n -= 8
+            b = (self.acc >> self.n) & 0xFF
+            self.out.append(b)
+            if b == 0xFF:
+                self.out.append(0)
+        self.acc &= (1 << self.n) - 1
 
     def flush(self):  # pad with 1 bits (T.81 F.1.2.3)
         if self.n:
@@ -170,7 +171,10 @@ class _ScanCoder:
             code, ln = self.tables[slot][s]
             self.w.bits(code, ln)
         else:
-            self.freq.setdefault(slot, np.zeros(256, np.int64))[s] += 1
+            f = self.freq.get(slot)
+            if f is None:
+                f = self.freq[slot] = [0] * 256
+            f[s] += 1
 
     def raw(self, v: int, n: int):
         if self.emit and n:
@@ -243,8 +247,7 @@ def _code_scan(frame, coefs, scan, coder: _ScanCoder, ri: int):
                 coder.sym(("dc", k), n)
                 coder.raw(_extra(d, n), n)
                 r = 0
-                for z in range(1, 64):
-                    v = int(blk[ZIGZAG[z]])
+                for v in blk[ZIGZAG[1:]].tolist():
                     if v == 0:
                         r += 1
                         continue
