@@ -2702,8 +2702,6 @@ __device__ bool params_valid(const dino_view_params& p, const ImgDesc& d, int S)
   return true;
 }
 
-__device__ int hr_view_chunks(int S, int cw, int ch, int kh);
-
 // k_vsizes: one lane per view: validity and scratch bytes into plan[i] (htmp_off holds
 // the size and rcoef_off the offset of the coefficient tables inside it until k_vplan
 // places the view), so that the single-workgroup scan only reads packed records.
@@ -2725,7 +2723,9 @@ __global__ void __launch_bounds__(256) k_vsizes(const ImgDesc* __restrict__ desc
   vp.kv = kv;
   vp.htmp_off = a;
   vp.rcoef_off = kh ? align16((int64_t)prm[i].crop_h * S * 3) : 0;
-  vp.hr_chunks = ok && kh ? hr_view_chunks(S, prm[i].crop_w, prm[i].crop_h, kh) : 0;
+  // (a vertical-first view is resampled by k_rcoeffs: no k_hresize items)
+  const bool vfirst = ok && resample_vfirst(prm[i].crop_w, prm[i].crop_h, view_rh(prm[i]), kh);
+  vp.hr_chunks = ok && kh && !vfirst ? hr_view_chunks(S, prm[i].crop_w, prm[i].crop_h, kh) : 0;
   vp.hr_base = 0;
   plan[i] = vp;
 }
@@ -2812,8 +2812,9 @@ __global__ void __launch_bounds__(1024) k_vplan(ImgDesc* __restrict__ desc, cons
   }
 }
 
-__global__ void __launch_bounds__(256) k_rcoeffs(const dino_view_params* __restrict__ prm, const ViewPlan* __restrict__ plan,
-                                                 int nv, int v0, uint8_t* __restrict__ aws) {
+__global__ void __launch_bounds__(256) k_rcoeffs(const ImgDesc* __restrict__ desc, const dino_view_params* __restrict__ prm,
+                                                 const ViewPlan* __restrict__ plan, int nv, int v0,
+                                                 const uint8_t* __restrict__ ws, uint8_t* __restrict__ aws) {
   const int i = blockIdx.y * nv + v0 + blockIdx.x;
   const ViewPlan vp = plan[i];
   if (!vp.ok) return;
@@ -2858,6 +2859,45 @@ __global__ void __launch_bounds__(256) k_rcoeffs(const dino_view_params* __restr
     if (vp.kv)
       resample_coeffs_one(p.crop_h, view_rh(p), p.out_y + x, vp.kv, &vb[2 * x], &vb[2 * x + 1], vt + (int64_t)x * vp.kv);
   }
+  if (!resample_vfirst(p.crop_w, p.crop_h, view_rh(p), vp.kh)) return;
+  // Vertical pass first (resample_vfirst: a crop over 100 times as high as wide, which no
+  // RandomResizedCrop draws; Pillow rounds its 8-bit intermediate in this order).  This
+  // workgroup resamples the whole view, an output row at a time: the row's vertical pass over
+  // the crop's columns into LDS, then its horizontal pass into row y of the temp planes,
+  // where k_hresize (which has no items of this view) would have put crop row y.  The
+  // vertical tables then become the identity on those rows, so that k_vert / k_vfinal copy.
+  __shared__ uint8_t s_row[3 * kVFirstMaxW];
+  const ImgDesc& d = desc[blockIdx.y];
+  const int cw = p.crop_w;
+  const int64_t spitch = (int64_t)d.width * 3, cpl = (int64_t)p.crop_h * S;
+  const uint8_t* src = ws + d.rgb_off + (int64_t)p.crop_top * spitch + (int64_t)p.crop_left * 3;
+  uint8_t* tmp = aws + vp.htmp_off;
+  __syncthreads();  // the tables above
+  for (int y = 0; y < S; ++y) {
+    const int ymin = vb[2 * y], ycnt = vb[2 * y + 1];
+    const int32_t* kv = vt + (int64_t)y * vp.kv;
+    for (int e = threadIdx.x; e < 3 * cw; e += blockDim.x) {
+      const uint8_t* q = src + (int64_t)ymin * spitch + e;
+      int32_t acc = 1 << (kPrecisionBits - 1);
+      for (int t = 0; t < ycnt; ++t) acc += (int32_t)q[(int64_t)t * spitch] * kv[t];
+      s_row[e] = clip8_acc(acc);
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 3 * S; e += blockDim.x) {
+      const int c = e / S, x = e - c * S;
+      const int xmin = hb[2 * x], xcnt = hb[2 * x + 1];
+      const int32_t* kk = ht + (int64_t)x * vp.kh;
+      int32_t acc = 1 << (kPrecisionBits - 1);
+      for (int t = 0; t < xcnt; ++t) acc += (int32_t)s_row[3 * (xmin + t) + c] * kk[t];
+      tmp[c * cpl + (int64_t)y * S + x] = clip8_acc(acc);
+    }
+    __syncthreads();
+  }
+  for (int y = threadIdx.x; y < S; y += blockDim.x) {
+    vb[2 * y] = y;
+    vb[2 * y + 1] = 1;
+    vt[(int64_t)y * vp.kv] = 1 << kPrecisionBits;
+  }
 }
 
 // Horizontal pass.  A workgroup owns bands of R source rows of one view.  The
@@ -2866,64 +2906,8 @@ __global__ void __launch_bounds__(256) k_rcoeffs(const dino_view_params* __restr
 // staged in LDS too when they fit.  Each lane then resamples one (row, x) with
 // one LDS word per tap and writes the three channels to planar temp rows
 // [3][crop_h][S].  Crops too wide for LDS take a direct (global) path.
-constexpr int kHresizeMinRows = 8;  // rows per band the slice width is chosen for
-constexpr int kHrBandsPerItem = 8;  // row bands of one slice per work item
-constexpr int kHrDirectItems = 4;  // work items of a direct-path view
+// The tile shape (hresize_tile, hr_view_chunks) is in hresize_tile.hpp.
 constexpr int kHrStageUnroll = 4;  // staging loads in flight per lane (2: 168.0k, 8: 168.8k, 4: 170.2k img/s C2)
-
-// Tile shape of a view's horizontal pass: the widest slice of outputs (all of S,
-// else a multiple of 8) whose taps (16 bytes per output + 16 per output and group
-// of 4 taps) and kHresizeMinRows staged rows fit kHresizeLds; then as many rows per
-// band as fit (<= 16).  R = 0: even 8 outputs do not fit (direct path).
-struct HrTile {
-  int sw, pitch, R, R3p;
-};
-__device__ __forceinline__ int hresize_pitch(int S, int cw, int kh, int sw) {
-  // widest source span of a slice (+ 4 for the word alignment of its first column)
-  const int span = min(cw, (int)(((int64_t)sw * cw + S - 1) / S) + kh + 2) + 4;
-  return ((span + 3) & ~3) + 8;  // + slack for the last group's upper word
-}
-// Words per staged source group: 3 R row-channel words + 2, rounded to 2 mod 4.  Even, so
-// a row pair's six words are one 8-byte-aligned run; 2 mod 4, so the row pairs that the
-// lanes of a ds_read_b64 group read at distinct source groups k fall on distinct bank
-// pairs (k R3p mod 64): with R = 10 or 14 (R3p 32 / 44) up to 16-way conflicts, 52 % of
-// the kernel's LDS cycles (SQ_LDS_BANK_CONFLICT, profiles/r05_c2_lds.txt).
-__host__ __device__ __forceinline__ int hresize_r3p(int R) {
-  const int r = 3 * R + 2;
-  return (r & 3) == 0 ? r + 2 : r;
-}
-// LDS bytes of a band of R rows: (pitch / 4) source words x R3p row-channel words,
-// plus room for the over-read of the last output's zero-tap groups (ng_max words).
-__device__ __forceinline__ int hresize_rows_bytes(int pitch, int R, int ng_max) {
-  return (pitch / 4 + ng_max + 1) * hresize_r3p(R) * 4;
-}
-__device__ __forceinline__ HrTile hresize_tile(int S, int cw, int kh) {
-  const int ng_max = (kh + 3) / 4;
-  const int tap_bytes = 16 * (1 + (ng_max | 1));
-  HrTile t{0, 0, 0, 0};
-  int sw = S;
-  while (tap_bytes * sw + hresize_rows_bytes(hresize_pitch(S, cw, kh, sw), kHresizeMinRows, ng_max) > kHresizeLds) {
-    sw = sw == S ? ((S - 1) & ~7) : sw - 8;
-    if (sw < 8) return t;
-  }
-  t.sw = sw;
-  t.pitch = hresize_pitch(S, cw, kh, sw);
-  int R = 16;
-  while (R > kHresizeMinRows && tap_bytes * sw + hresize_rows_bytes(t.pitch, R, ng_max) > kHresizeLds) R -= 2;
-  t.R = R;
-  t.R3p = hresize_r3p(R);
-  return t;
-}
-
-// Work items of a view's horizontal pass (k_vsizes): kHrBandsPerItem row bands of one
-// slice each, so that a batch of mixed crop sizes spreads over the persistent grid in
-// pieces of similar size (a large crop's view is many items, a small one's few).
-__device__ int hr_view_chunks(int S, int cw, int ch, int kh) {
-  const HrTile t = hresize_tile(S, cw, kh);
-  if (t.R < 1) return kHrDirectItems;
-  const int nsl = (S + t.sw - 1) / t.sw, nbands = (ch + t.R - 1) / t.R;
-  return nsl * ((nbands + kHrBandsPerItem - 1) / kHrBandsPerItem);
-}
 
 // The view of work item c among the nc class views (b, v0 + j), j = view index mod nvc:
 // the last view whose first item is <= c (views without items share their successor's
@@ -4267,7 +4251,7 @@ static hipError_t launch_augment_class(const AugmentArgs& a, int v0, int nvc, in
   const int kfin = v0 == 0 ? kKFinalGlobal : kKFinalLocal;
   const int kvert = v0 == 0 ? kKVertGlobal : kKVertLocal;
   const int rc_threads = S < 256 ? (S + 63) / 64 * 64 : 256;  // one lane per output column
-  TIMED(tm, kKRcoeffs, s, (k_rcoeffs<<<dim3(nvc, B), rc_threads, 0, s>>>(a.params, a.plan, nv, v0, a.aws)));
+  TIMED(tm, kKRcoeffs, s, (k_rcoeffs<<<dim3(nvc, B), rc_threads, 0, s>>>(a.desc, a.params, a.plan, nv, v0, a.ws, a.aws)));
   TIMED(tm, kKHresize, s,
         (k_hresize<<<a.grid_hr, 256, kHresizeLds, s>>>(a.desc, a.params, a.plan, nv, v0, nvc, B, a.ws, a.aws)));
   if (S <= kVFinalMaxS) {  // small views: vertical pass and epilogue fused, the view stays in LDS

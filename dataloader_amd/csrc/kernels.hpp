@@ -2,6 +2,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "hresize_tile.hpp"
 
 namespace dino {
 
@@ -14,9 +15,6 @@ constexpr int kHuffThreads = 256;
 #define DINO_HUFF_SEG_KBITS 2048
 #endif
 constexpr int64_t kHuffSegBits = (int64_t)DINO_HUFF_SEG_KBITS * 1024;
-
-// LDS of k_hresize: taps (when they fit in kHresizeTapLds) + planar rows of one band.
-constexpr int kHresizeLds = 26 * 1024;
 
 struct ViewPlan {
   int64_t htmp_off;   // horizontal-pass rows (crop_h x S x 3 u8) in the augment workspace

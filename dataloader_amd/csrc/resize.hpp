@@ -67,6 +67,16 @@ DHD void resample_coeffs_one(int in_size, int out_size, int xx, int ksize, int32
   *xmax_out = xmax;
 }
 
+// Pillow's Image.resize (as of 12.2) resamples an image more than 100 times as high as
+// wide, when its height shrinks, in two calls with the vertical pass first, so the 8-bit
+// intermediate is rounded in the other order.  True for a crop of cw x ch resampled to a
+// height of rh with kh horizontal taps (0: no horizontal pass, the order is moot).
+// Such a crop is at most kVFirstMaxW wide (sides are <= 65536).
+constexpr int kVFirstMaxW = 656;
+DHD bool resample_vfirst(int cw, int ch, int rh, int kh) {
+  return kh != 0 && (int64_t)ch > (int64_t)cw * 100 && rh < ch && cw <= kVFirstMaxW;
+}
+
 // clip8 of the fixed-point accumulator (Resample.c).
 DHD uint8_t clip8_acc(int32_t in) {
   if (in >= (1 << kPrecisionBits << 8)) return 255;

@@ -17,6 +17,7 @@
 #include "../../dataloader_amd/csrc/jpeg_parse.hpp"
 #include "../../dataloader_amd/csrc/pixel_ops.hpp"
 #include "../../dataloader_amd/csrc/resize.hpp"
+#include "../../dataloader_amd/csrc/hresize_tile.hpp"
 #include "../../dataloader_amd/csrc/augment.hpp"
 #include "../../dataloader_amd/csrc/mask.hpp"
 #include "models.hpp"
@@ -150,6 +151,20 @@ int emu_augment_view(const uint8_t* rgb, int W, int H, const dino_view_params* v
 int emu_resized_crop(const uint8_t* rgb, int W, int H, const dino_view_params* vp, uint8_t* out) {
   return host_model_resized_crop(rgb, W, H, *vp, out);
 }
+
+// Tile shape of k_hresize for a crop of cw x ch at view size S with kh taps (the kernel's
+// own hresize_tile / hr_view_chunks): out = {sw, pitch, R, R3p, work items}.  R = 0: direct path.
+void emu_hresize_tile(int S, int cw, int ch, int kh, int32_t* out) {
+  const HrTile t = hresize_tile(S, cw, kh);
+  out[0] = t.sw;
+  out[1] = t.pitch;
+  out[2] = t.R;
+  out[3] = t.R3p;
+  out[4] = hr_view_chunks(S, cw, ch, kh);
+}
+
+// Pillow's tap count for in_size -> out_size (0: the axis is not resampled).
+int emu_resample_ksize(int in_size, int out_size) { return in_size == out_size ? 0 : resample_ksize(in_size, out_size); }
 
 // ---- masks ----------------------------------------------------------------------
 int emu_masks(int H, int W, int target, int minp, int maxp, double la0, double la1, int n, uint32_t* py_state,

@@ -454,6 +454,23 @@ inline void model_resize_planar(const uint8_t* rgb, int W, int H, const dino_vie
   const bool need_h = p.crop_w != S, need_v = p.crop_h != S;
   SrcView src{rgb + ((int64_t)p.crop_top * W + p.crop_left) * 3, (int64_t)W * 3, 3, 1};
   ViewModel vm;
+  if (need_h && need_v && resample_vfirst(p.crop_w, p.crop_h, S, resample_ksize(p.crop_w, S))) {
+    // vertical pass first (k_rcoeffs): planar [3][S][crop_w], then the horizontal pass
+    model_coeffs(p.crop_h, S, vm.vb, vm.vt, vm.kv);
+    model_coeffs(p.crop_w, S, vm.hb, vm.ht, vm.kh);
+    CoefView cvv{vm.vb.data(), vm.vt.data(), vm.kv}, cv{vm.hb.data(), vm.ht.data(), vm.kh};
+    const int cw = p.crop_w;
+    vm.tmp.assign((size_t)S * cw * 3, 0);
+    for (int y = 0; y < S; ++y)
+      for (int x = 0; x < cw; ++x)
+        for (int ch = 0; ch < 3; ++ch) vm.tmp[(size_t)ch * S * cw + (size_t)y * cw + x] = vresize_at(src, cvv, y, x, ch);
+    src = SrcView{vm.tmp.data(), (int64_t)cw, 1, (int64_t)S * cw};
+    for (int y = 0; y < S; ++y)
+      for (int x = 0; x < S; ++x)
+        for (int ch = 0; ch < 3; ++ch)
+          planes[(size_t)ch * S * S + (size_t)y * S + (p.flip ? S - 1 - x : x)] = hresize_at(src, cv, y, x, ch);
+    return;
+  }
   if (need_h) {
     model_coeffs(p.crop_w, S, vm.hb, vm.ht, vm.kh);
     CoefView cv{vm.hb.data(), vm.ht.data(), vm.kh};

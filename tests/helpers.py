@@ -111,6 +111,97 @@ def emu_resized_crop(lib, rgb: np.ndarray, rec) -> np.ndarray:
     return out.reshape(S, S, 3)
 
 
+def hresize_tile(lib, S: int, cw: int, ch: int = 1):
+    """k_hresize's tile shape for a cw x ch crop at view size S, from the kernel's own
+    functions: (sw, pitch, R, R3p, work items, tap groups).  R == 0 is the direct path."""
+    kh = lib.emu_resample_ksize(cw, S)
+    out = (ctypes.c_int32 * 5)()
+    lib.emu_hresize_tile(S, cw, ch, kh, out)
+    return (*out, (kh + 3) // 4)
+
+
+SWEEP_SIZES = (30, 96, 128, 132, 224, 518, 1024)
+SWEEP_MAX_WIDTH = 2048          # widest raw image of the two large view sizes
+SWEEP_DIRECT_SIZES = (30, 96, 224)  # view sizes whose list goes on to the direct-path pair
+SWEEP_WALK_LIMIT = 20000        # the view sizes <= 256 are on the direct path well before
+
+
+def hresize_shape_table(lib, S: int):
+    """[(first width, last width, sw, R)] of every (sw, R) shape as the crop width rises from
+    1 to the first direct-path width (whose entry, R == 0, ends the table; for S > 256 the
+    walk ends at SWEEP_MAX_WIDTH instead, the last entry cut there), and the first width with
+    more than 8 tap groups (the generic group loop).  crop_w == S has no horizontal pass and
+    belongs to no shape."""
+    table, first_ng = [], None
+    for cw in range(1, SWEEP_MAX_WIDTH + 1 if S > 256 else SWEEP_WALK_LIMIT):
+        if cw == S:
+            continue
+        sw, _, R, _, _, ng = hresize_tile(lib, S, cw)
+        if first_ng is None and ng > 8 and R > 0:
+            first_ng = cw
+        if not table or table[-1][2:] != (sw, R):
+            table.append((cw, cw, sw, R))
+        else:
+            table[-1] = (table[-1][0], cw, sw, R)
+        if R == 0:
+            return table, first_ng
+    assert S > 256, f"S={S}: no direct-path width below {SWEEP_WALK_LIMIT}"
+    return table, first_ng
+
+
+def resample_sweep_widths(lib, S: int) -> list[int]:
+    """Crop widths that pin every tile shape of k_hresize at view size S: the first and the
+    last width of each (sw, R) shape and the first width with more than 8 tap groups;
+    up to SWEEP_MAX_WIDTH for S > 256, up to the last staged shape for the others, and the
+    direct-path pair (last staged width, first direct width) for SWEEP_DIRECT_SIZES."""
+    table, first_ng = hresize_shape_table(lib, S)
+    ws = set()
+    for first, last, _, R in table:
+        if R == 0:
+            if S in SWEEP_DIRECT_SIZES:
+                ws.add(first)
+            continue
+        ws.update((first, last))
+    if first_ng is not None:
+        ws.add(first_ng)
+    return sorted(ws)
+
+
+def saturating_rgb(w: int, h: int, rng) -> np.ndarray:
+    """Content whose bicubic resample overshoots 0 and 255 (it must clip), in four bands of
+    rows: independent 0/255 bits per channel, a 1-px checkerboard, 0/255 stripes of period 3
+    along x, and uniform u8 noise."""
+    img = np.empty((h, w, 3), np.uint8)
+    yy, xx = np.mgrid[0:h, 0:w]
+    q = [h * k // 4 for k in range(5)]
+    img[q[0]:q[1]] = rng.integers(0, 2, size=(q[1] - q[0], w, 3), dtype=np.uint8) * 255
+    img[q[1]:q[2]] = (((xx + yy) & 1) * 255).astype(np.uint8)[q[1]:q[2], :, None]
+    img[q[2]:q[3]] = ((xx % 3 == 0) * 255).astype(np.uint8)[q[2]:q[3], :, None]
+    img[q[3]:q[4]] = rng.integers(0, 256, size=(q[4] - q[3], w, 3), dtype=np.uint8)
+    return img
+
+
+def pillow_bicubic_row_unclipped(row: np.ndarray, out_size: int) -> np.ndarray:
+    """One row through Pillow's BICUBIC coefficient formula (Resample.c precompute_coeffs,
+    a = -0.5, normalised weights) in float64, without the 8-bit clip."""
+    def f(x):
+        x = np.abs(x)
+        return np.where(x < 1.0, ((1.5 * x - 2.5) * x) * x + 1.0,
+                        np.where(x < 2.0, (((x - 5.0) * x + 8.0) * x - 4.0) * -0.5, 0.0))
+    n = len(row)
+    scale = n / out_size
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    out = np.empty(out_size)
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        x0 = max(0, int(center - support + 0.5))
+        x1 = min(n, int(center + support + 0.5))
+        k = f((np.arange(x0, x1) - center + 0.5) / fs)
+        out[xx] = float(np.dot(k / k.sum(), row[x0:x1].astype(np.float64)))
+    return out
+
+
 def dc_extremes_rgb(w: int, h: int, rng, cell: int = 16) -> np.ndarray:
     """Saturated colour cells (black/white/blue/yellow/red/cyan) in cell x cell squares:
     neighbouring blocks differ by DC categories 10-11 in luma and chroma, whose chroma

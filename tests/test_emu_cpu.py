@@ -78,6 +78,12 @@ def test_normalize_and_casts(emu):
     o = np.zeros(x.size, np.uint8)
     emu.emu_fp8(x.ctypes.data_as(P), x.size, o.ctypes.data_as(P))
     np.testing.assert_array_equal(o, torch.from_numpy(x).to(torch.float8_e4m3fn).view(torch.uint8).numpy())
+    # every bf16 bit pattern: NaN payloads, infinities, saturation at +-448, subnormals, ties
+    allbf = torch.arange(65536, dtype=torch.int32).to(torch.int16).view(torch.bfloat16)
+    x = allbf.float().numpy()
+    o = np.zeros(x.size, np.uint8)
+    emu.emu_fp8(x.ctypes.data_as(P), x.size, o.ctypes.data_as(P))
+    np.testing.assert_array_equal(o, allbf.to(torch.float8_e4m3fn).view(torch.uint8).numpy())
 
 
 def _zoo():
@@ -211,6 +217,23 @@ def test_resized_crop_bit_exact(emu):
             if p.flip:
                 ref = ref.transpose(Image.FLIP_LEFT_RIGHT)
             np.testing.assert_array_equal(emu_resized_crop(emu, rgb, params_to_record(p)), np.asarray(ref))
+
+
+def test_resized_crop_vertical_pass_first(emu):
+    """Pillow resamples a crop over 100 times as high as wide, when its height shrinks, with
+    the vertical pass first (resample_vfirst): both sides of the 100 x rule, a height that
+    grows, no horizontal pass, and the flip, on noise (the two orders round differently)."""
+    rng = np.random.default_rng(7)
+    rgb = rng.integers(0, 256, size=(4001, 34, 3), dtype=np.uint8)
+    img = Image.fromarray(rgb)
+    for S, left, top, cw, ch, flip in [(30, 1, 0, 31, 4001, False), (30, 0, 0, 31, 3101, True), (30, 3, 7, 31, 3100, False),
+                                       (30, 2, 0, 30, 4001, True), (30, 0, 1, 7, 4000, True), (16, 5, 0, 1, 101, False),
+                                       (40, 33, 9, 1, 39, False), (30, 4, 0, 29, 2901, False)]:
+        p = cpu_ref.ViewParams(out_size=S, crop_top=top, crop_left=left, crop_h=ch, crop_w=cw, flip=flip)
+        ref = cpu_ref.resized_crop(img, top, left, ch, cw, S)
+        if flip:
+            ref = ref.transpose(Image.FLIP_LEFT_RIGHT)
+        np.testing.assert_array_equal(emu_resized_crop(emu, rgb, params_to_record(p)), np.asarray(ref), err_msg=str((S, cw, ch)))
 
 
 def test_augment_views_vs_oracle(emu):

@@ -170,6 +170,17 @@ def test_fp8_formatter(gpu_device):
     assert got.dtype == torch.float8_e4m3fn
     ref = x.cpu().to(torch.float8_e4m3fn)
     assert torch.equal(got.cpu().view(torch.uint8), ref.view(torch.uint8))
+    # every bf16 bit pattern (NaN payloads, infinities, saturation at +-448, subnormals, ties),
+    # whole, with a ragged tail (no multiple of the block), and through non-contiguous views
+    allbf = torch.arange(65536, dtype=torch.int32).to(torch.int16).view(torch.bfloat16)
+    d_all = allbf.to(gpu_device)
+    grid = d_all.view(256, 256)
+    for name, x in [("all", d_all), ("ragged", d_all[:65536 - 3]), ("offset", d_all[3:]), ("strided", d_all[::3]),
+                    ("transposed", grid.t()), ("columns", grid[:, 5:250])]:
+        got = HipFP8Formatter().quantise(x)
+        assert got.dtype == torch.float8_e4m3fn and got.shape == x.shape, name
+        ref = x.cpu().to(torch.float8_e4m3fn)
+        assert torch.equal(got.cpu().contiguous().view(torch.uint8), ref.contiguous().view(torch.uint8)), name
 
 
 def test_pipeline_iterator_and_close(gpu_device):
