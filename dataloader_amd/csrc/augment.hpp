@@ -33,7 +33,7 @@ DHD uint8_t hresize_at(const SrcView& s, const CoefView& cv, int row, int x, int
   const int32_t* k = cv.taps + (int64_t)x * cv.ksize;
   const uint8_t* p = s.base + (int64_t)row * s.pitch + (int64_t)xmin * s.px + ch * s.cs;
   int32_t acc = 1 << (kPrecisionBits - 1);
-  for (int t = 0; t < xcnt; ++t) acc += (int32_t)p[t * s.px] * k[t];
+  for (int t = 0; t < xcnt; ++t) acc = tap_mad(p[t * s.px], k[t], acc);
   return clip8_acc(acc);
 }
 
@@ -42,7 +42,7 @@ DHD uint8_t vresize_at(const SrcView& s, const CoefView& cv, int y, int x, int c
   const int32_t* k = cv.taps + (int64_t)y * cv.ksize;
   const uint8_t* p = s.base + (int64_t)ymin * s.pitch + (int64_t)x * s.px + ch * s.cs;
   int32_t acc = 1 << (kPrecisionBits - 1);
-  for (int t = 0; t < ycnt; ++t) acc += (int32_t)p[(int64_t)t * s.pitch] * k[t];
+  for (int t = 0; t < ycnt; ++t) acc = tap_mad(p[(int64_t)t * s.pitch], k[t], acc);
   return clip8_acc(acc);
 }
 

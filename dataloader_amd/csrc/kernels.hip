@@ -2879,7 +2879,7 @@ __global__ void __launch_bounds__(256) k_rcoeffs(const ImgDesc* __restrict__ des
     for (int e = threadIdx.x; e < 3 * cw; e += blockDim.x) {
       const uint8_t* q = src + (int64_t)ymin * spitch + e;
       int32_t acc = 1 << (kPrecisionBits - 1);
-      for (int t = 0; t < ycnt; ++t) acc += (int32_t)q[(int64_t)t * spitch] * kv[t];
+      for (int t = 0; t < ycnt; ++t) acc = tap_mad(q[(int64_t)t * spitch], kv[t], acc);
       s_row[e] = clip8_acc(acc);
     }
     __syncthreads();
@@ -2888,7 +2888,7 @@ __global__ void __launch_bounds__(256) k_rcoeffs(const ImgDesc* __restrict__ des
       const int xmin = hb[2 * x], xcnt = hb[2 * x + 1];
       const int32_t* kk = ht + (int64_t)x * vp.kh;
       int32_t acc = 1 << (kPrecisionBits - 1);
-      for (int t = 0; t < xcnt; ++t) acc += (int32_t)s_row[3 * (xmin + t) + c] * kk[t];
+      for (int t = 0; t < xcnt; ++t) acc = tap_mad(s_row[3 * (xmin + t) + c], kk[t], acc);
       tmp[c * cpl + (int64_t)y * S + x] = clip8_acc(acc);
     }
     __syncthreads();
@@ -3226,23 +3226,28 @@ __device__ __forceinline__ uint32_t vert_apply(const ImgDesc& d, const dino_view
       uint32_t w[3];
       if (need_v) {
         const int ymin = cvv.bounds[2 * y], ycnt = cvv.bounds[2 * y + 1];
-        const int32_t* k = cvv.taps + (int64_t)y * cvv.ksize;
         // taps outer, channels inner: one tap load serves the three planes, whose
-        // three row loads are independent (exact int32 sums: the order is free)
-        const uint8_t* q = htmp + (int64_t)ymin * S + 4 * xq;
+        // three row loads are independent (exact int32 sums: the order is free).
+        // Addresses are the view's uniform bases plus 32-bit byte offsets that step by a
+        // row per tap (3 crop_h S < 2^28, 4 S ksize < 2^30): no 64-bit multiply per tap.
+        uint32_t ko = 4u * (uint32_t)(y * cvv.ksize);
+        uint32_t qo[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) qo[c] = (uint32_t)(ymin * S + 4 * xq) + (uint32_t)c * (uint32_t)cpl;
         int32_t a[3][4];
 #pragma unroll
         for (int c = 0; c < 3; ++c) a[c][0] = a[c][1] = a[c][2] = a[c][3] = 1 << (kPrecisionBits - 1);
 #pragma unroll 2
-        for (int t = 0; t < ycnt; ++t) {
-          const int32_t kk = k[t];
+        for (int t = 0; t < ycnt; ++t, ko += 4u) {
+          const int32_t kk = *(const int32_t*)((const uint8_t*)cvv.taps + ko);
 #pragma unroll
           for (int c = 0; c < 3; ++c) {
-            const uint32_t u = *(const uint32_t*)(q + c * cpl + (int64_t)t * S);
-            a[c][0] += (int32_t)(u & 255u) * kk;
-            a[c][1] += (int32_t)((u >> 8) & 255u) * kk;
-            a[c][2] += (int32_t)((u >> 16) & 255u) * kk;
-            a[c][3] += (int32_t)(u >> 24) * kk;
+            const uint32_t u = *(const uint32_t*)(htmp + qo[c]);
+            qo[c] += (uint32_t)S;
+            a[c][0] = tap_mad((int32_t)(u & 255u), kk, a[c][0]);
+            a[c][1] = tap_mad((int32_t)((u >> 8) & 255u), kk, a[c][1]);
+            a[c][2] = tap_mad((int32_t)((u >> 16) & 255u), kk, a[c][2]);
+            a[c][3] = tap_mad((int32_t)(u >> 24), kk, a[c][3]);
           }
         }
 #pragma unroll

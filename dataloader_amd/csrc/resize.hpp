@@ -67,6 +67,33 @@ DHD void resample_coeffs_one(int in_size, int out_size, int xx, int ksize, int32
   *xmax_out = xmax;
 }
 
+// acc + px * k for one 8-bit pixel and one tap of resample_coeffs_one, as a 24-bit signed
+// multiply-add on the GPU (v_mad_i32_i24, full rate; the 32-bit multiply it replaces issues
+// at a quarter of that).  Both return the same low 32 bits whenever each operand is its own
+// sign extension from 24 bits, so the sums stay Pillow's.  px is 0..255.  |k| < 2^23:
+// a tap is round(2^22 w / ww) with w = bicubic_filter(d) and ww the sum of the window's
+// weights.  The window always holds the pixel whose centre is nearest the output's centre
+// (that centre lies inside the image, and clipping at an edge removes taps on the far side
+// of it only), at |d| <= 0.5, and every pixel between it and the window's ends.  The filter
+// is positive over |d| < 1 (area 1.0833) and negative over 1 < |d| < 2 (area -0.0417 a
+// side, never below -2/27).  Upscaling (tap spacing 1): the weights left are f(d) >= 0.5625
+// and at most one more positive and two negative ones, so ww >= 0.5625 - 4/27 = 0.41 and
+// |w / ww| <= 1 / 0.41 < 2; the worst case is a window clipped to f(0.5), f(1.5) =
+// 0.5625, -0.0625, whose larger tap is 1.125.  Downscaling by s samples the same filter
+// s times as densely, with the nearest pixel at |d| <= 0.5 / s: the positive lobe's taps
+// sum to at least 0.54 s - 1 beside a largest weight of 1 and negative ones of at most
+// 0.084 s + 4/27, which leaves the ratio smaller still.
+// The identity tap 2^22 (a pass that only copies) is inside the range too.
+// tests/test_rcoeffs_range_cpu.py sweeps sizes, scales and edge positions for the largest
+// magnitude (1.125 x 2^22); k_hresize's digit split needs the same bound (k_rcoeffs).
+DHD int32_t tap_mad(int32_t px, int32_t k, int32_t acc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __mul24(px, k) + acc;
+#else
+  return px * k + acc;
+#endif
+}
+
 // Pillow's Image.resize (as of 12.2) resamples an image more than 100 times as high as
 // wide, when its height shrinks, in two calls with the vertical pass first, so the 8-bit
 // intermediate is rounded in the other order.  True for a crop of cw x ch resampled to a
