@@ -113,6 +113,85 @@ __global__ void __launch_bounds__(64) k_parse(const uint8_t* __restrict__ bytes,
 }
 
 // ---------------------------------------------------------------------------
+// Workgroup scans
+// ---------------------------------------------------------------------------
+// Exclusive scan of one word per lane over NT lanes (wave shuffles + one LDS word per wave).
+template <int NT>
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_wave, uint32_t* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  uint32_t x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t y = __shfl_up(x, o);
+    if (lane >= o) x += y;
+  }
+  if (lane == 63) s_wave[w] = x;
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+#pragma unroll
+  for (int k = 0; k < NT / 64; ++k) {
+    const uint32_t t = s_wave[k];
+    before += k < w ? t : 0u;
+    all += t;
+  }
+  __syncthreads();
+  *total = all;
+  return before + x - v;
+}
+
+// The planners (k_plan, k_vplan, k_dplan: one workgroup of 1024 lanes): n items in batch
+// order, size(i) a V or something that converts to one (V::bytes of workspace plus whatever
+// else the kernel counts per item, summed with +; bytes == 0: nothing to place).  Each lane
+// sums its run of items, a Hillis-Steele scan over the lanes gives every item the exclusive
+// sum of the items before it, and when the batch's bytes fit `cap` every lane calls
+// place(i, what size(i) returned, base, true) for its items.  Otherwise lane 0 alone walks
+// the batch: an item goes at the bytes placed so far when it still fits (place(..., true)),
+// and else gets place(..., false) and, if it has bytes, reject(i), so that an item that
+// does not fit leaves its room to the later ones.  The other members of base are the sums
+// over every item before i in both cases.  Both branches size an item by the one size(i).
+template <typename V, typename Size, typename Place, typename Reject>
+__device__ __forceinline__ void scan_and_place(int n, int64_t cap, Size size, Place place, Reject reject) {
+  __shared__ V part[1024];
+  const int t = threadIdx.x;
+  const int per = (n + 1023) / 1024;
+  V local{};
+  for (int k = 0; k < per; ++k) {
+    const int i = t * per + k;
+    if (i < n) local = local + V(size(i));
+  }
+  part[t] = local;
+  __syncthreads();
+  for (int s = 1; s < 1024; s <<= 1) {  // Hillis-Steele inclusive scan
+    const V v = t >= s ? part[t - s] : V{};
+    __syncthreads();
+    part[t] = part[t] + v;
+    __syncthreads();
+  }
+  if (part[1023].bytes <= cap) {
+    V base = t ? part[t - 1] : V{};
+    for (int k = 0; k < per; ++k) {
+      const int i = t * per + k;
+      if (i >= n) continue;
+      const auto v = size(i);
+      place(i, v, base, true);
+      base = base + V(v);
+    }
+  } else if (t == 0) {
+    V base{};
+    for (int i = 0; i < n; ++i) {
+      const auto it = size(i);
+      const V v = it;
+      const bool placed = v.bytes != 0 && base.bytes + v.bytes <= cap;
+      place(i, it, base, placed);
+      if (v.bytes != 0 && !placed) reject(i);
+      const int64_t b = base.bytes;
+      base = base + v;
+      if (!placed) base.bytes = b;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // k_plan: exclusive scan of per-image chunk sizes (single workgroup of 1024)
 // ---------------------------------------------------------------------------
 // Places the image at `base` (or marks it DINO_IMG_NO_SPACE).
@@ -137,17 +216,23 @@ __device__ void plan_place(ImgDesc& d, const ChunkSizes& z, int64_t base, int64_
   d.h_lanes_cap = huff_lanes_cap(d);
 }
 
-// Exclusive scan of the images' chunk sizes.  When the batch does not fit the
-// workspace, images are accepted greedily in batch order instead (one lane), so
-// that an image that does not fit leaves its bytes to the later ones: only images
-// that cannot be placed get DINO_IMG_NO_SPACE (the host probe, dino_probe, sizes
-// the workspace so that this does not happen on the product path).
+// Exclusive scan of the images' chunk sizes (scan_and_place: greedy in batch order when
+// the batch does not fit the workspace; the host probe, dino_probe, sizes the workspace so
+// that this does not happen on the product path).
+struct __attribute__((packed, aligned(4))) ImgSum {  // 12 bytes a lane in LDS, as two arrays would take
+  int64_t bytes;
+  int32_t ds;  // destuff work items
+  __device__ ImgSum operator+(const ImgSum& o) const { return {bytes + o.bytes, ds + o.ds}; }
+};
+struct ImgItem {
+  ChunkSizes z;
+  int32_t ds;
+  __device__ operator ImgSum() const { return {z.total(), ds}; }
+};
+
 __global__ void __launch_bounds__(1024) k_plan(ImgDesc* __restrict__ desc, int B, int64_t ws_size,
                                               PCtl* __restrict__ pctl) {
-  __shared__ int64_t part[1024];
-  __shared__ int32_t dpart[1024];
-  const int t = threadIdx.x;
-  if (t == 0) {  // the batch's coefficient-buffer registry (k_pwalk, k_pscan, k_plscan)
+  if (threadIdx.x == 0) {  // the batch's coefficient-buffer registry (k_pwalk, k_pscan, k_plscan)
     pctl->ticket = 0;
     pctl->nprog = 0;
     pctl->max_scans = 0;
@@ -156,59 +241,15 @@ __global__ void __launch_bounds__(1024) k_plan(ImgDesc* __restrict__ desc, int B
     pctl->nlane = 0;
     pctl->lmax_scans = 0;
   }
-  const int per = (B + 1023) / 1024;
-  int64_t local = 0;
-  int32_t dlocal = 0;
-  for (int k = 0; k < per; ++k) {
-    int i = t * per + k;
-    if (i < B) {
-      local += image_chunk_bytes(desc[i]).total();
-      dlocal += ds_parts(desc[i]);
-    }
-  }
-  part[t] = local;
-  dpart[t] = dlocal;
-  __syncthreads();
-  for (int s = 1; s < 1024; s <<= 1) {  // Hillis-Steele inclusive scans
-    int64_t v = t >= s ? part[t - s] : 0;
-    int32_t dv = t >= s ? dpart[t - s] : 0;
-    __syncthreads();
-    part[t] += v;
-    dpart[t] += dv;
-    __syncthreads();
-  }
-  const bool fits = part[1023] <= ws_size;
-  int64_t base = part[t] - local;
-  int32_t dbase = dpart[t] - dlocal;
-  for (int k = 0; k < per; ++k) {
-    int i = t * per + k;
-    if (i >= B) continue;
-    ImgDesc& d = desc[i];
-    d.ds_item_base = dbase;
-    d.ds_items = ds_parts(d);  // as counted by the scan above (the kernels skip images not OK)
-    dbase += d.ds_items;
-    const ChunkSizes z = image_chunk_bytes(d);
-    if (fits) plan_place(d, z, base, ws_size);
-    base += z.total();
-  }
-  if (!fits) {
-    __syncthreads();
-    if (t == 0) {
-      int64_t b = 0;
-      for (int i = 0; i < B; ++i) {
+  scan_and_place<ImgSum>(
+      B, ws_size, [&](int i) { return ImgItem{image_chunk_bytes(desc[i]), ds_parts(desc[i])}; },
+      [&](int i, const ImgItem& v, const ImgSum& base, bool placed) {
         ImgDesc& d = desc[i];
-        const ChunkSizes z = image_chunk_bytes(d);
-        const int64_t sz = z.total();
-        if (sz == 0) continue;
-        if (b + sz <= ws_size) {
-          plan_place(d, z, b, ws_size);
-          b += sz;
-        } else {
-          d.status = DINO_IMG_NO_SPACE;
-        }
-      }
-    }
-  }
+        d.ds_item_base = base.ds;
+        d.ds_items = v.ds;  // (the kernels skip images not OK)
+        if (placed) plan_place(d, v.z, base.bytes, ws_size);
+      },
+      [&](int i) { desc[i].status = DINO_IMG_NO_SPACE; });
 }
 
 // ---------------------------------------------------------------------------
@@ -230,29 +271,6 @@ __device__ __forceinline__ int classify_ff(const uint8_t* r, int n, int k) {
 // aligned 16-byte chunk (plus the bytes either side for the 0xFF rules),
 // classifies it, and the workgroup scans (kept bytes, RST markers) packed in one
 // word to place the lane's output.  The first terminating marker ends the scan.
-template <int NT>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_wave, uint32_t* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_wave[w] = x;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < NT / 64; ++k) {
-    const uint32_t t = s_wave[k];
-    before += k < w ? t : 0u;
-    all += t;
-  }
-  __syncthreads();
-  *total = all;
-  return before + x - v;
-}
-
 // A lane's 16-byte chunk c of the scan, classified: bit j of keep = byte kept,
 // of rstm = an RSTn marker starts there; term = scan index of the first
 // terminating marker in the chunk (n if none).
@@ -2677,13 +2695,6 @@ __global__ void k_params(const ImgDesc* __restrict__ desc, int B, dino_aug_confi
 __device__ __forceinline__ int view_rw(const dino_view_params& p) { return p.resize_w > 0 ? p.resize_w : p.out_size; }
 __device__ __forceinline__ int view_rh(const dino_view_params& p) { return p.resize_h > 0 ? p.resize_h : p.out_size; }
 
-// Scratch of one view (plan.hpp view_scratch_bytes); 0 when the view is not rendered.
-__device__ void view_sizes(const dino_view_params& p, int ok, int64_t* bytes, int32_t* kh, int32_t* kv) {
-  *kh = ok && p.crop_w != view_rw(p) ? resample_ksize(p.crop_w, view_rw(p)) : 0;
-  *kv = ok && p.crop_h != view_rh(p) ? resample_ksize(p.crop_h, view_rh(p)) : 0;
-  *bytes = ok ? view_scratch_bytes(p.out_size, p.crop_w, p.crop_h, *kh, *kv) : 0;
-}
-
 // Host-supplied records are validated before any kernel indexes memory with them.
 __device__ bool params_valid(const dino_view_params& p, const ImgDesc& d, int S) {
   if (p.out_size != S) return false;
@@ -2713,103 +2724,56 @@ __global__ void __launch_bounds__(256) k_vsizes(const ImgDesc* __restrict__ desc
   const ImgDesc& d = desc[i / nv];
   const int S = (i % nv) < n_global ? gsize : lsize;
   const int ok = d.status == DINO_IMG_OK && params_valid(prm[i], d, S);
-  int64_t a;
-  int32_t kh, kv;
-  view_sizes(prm[i], ok, &a, &kh, &kv);
+  const dino_view_params& p = prm[i];
+  const int32_t kh = ok && p.crop_w != view_rw(p) ? resample_ksize(p.crop_w, view_rw(p)) : 0;
+  const int32_t kv = ok && p.crop_h != view_rh(p) ? resample_ksize(p.crop_h, view_rh(p)) : 0;
+  const ViewScratch L = view_scratch(S, p.crop_h, kh, kv);
   ViewPlan vp;
   vp.ok = ok;
   vp.lsum = 0;
   vp.kh = kh;
   vp.kv = kv;
-  vp.htmp_off = a;
-  vp.rcoef_off = kh ? align16((int64_t)prm[i].crop_h * S * 3) : 0;
+  vp.htmp_off = ok ? L.total : 0;  // 0: the view is not rendered
+  vp.rcoef_off = L.hb;
   // (a vertical-first view is resampled by k_rcoeffs: no k_hresize items)
-  const bool vfirst = ok && resample_vfirst(prm[i].crop_w, prm[i].crop_h, view_rh(prm[i]), kh);
-  vp.hr_chunks = ok && kh && !vfirst ? hr_view_chunks(S, prm[i].crop_w, prm[i].crop_h, kh) : 0;
+  const bool vfirst = ok && resample_vfirst(p.crop_w, p.crop_h, view_rh(p), kh);
+  vp.hr_chunks = ok && kh && !vfirst ? hr_view_chunks(S, p.crop_w, p.crop_h, kh) : 0;
   vp.hr_base = 0;
   plan[i] = vp;
 }
 
-// Per-view scratch offsets: exclusive scan of the views' scratch sizes, or (when the
-// batch's views do not fit the augment workspace) greedy placement in batch order by
-// one lane.  A view that cannot be placed is not rendered and its image is marked
+// Per-view scratch offsets and k_hresize work-item bases from k_vsizes' records
+// (scan_and_place).  A view that cannot be placed is not rendered and its image is marked
 // DINO_IMG_NO_SPACE (reported by dino_batch_info; the host sizes the workspace with
 // dino_probe + dino_reserve so that this does not happen on the product path).
+struct ViewSum {
+  int64_t bytes;
+  int32_t hg, hl;  // k_hresize work items of the global / local views
+  __device__ ViewSum operator+(const ViewSum& o) const { return {bytes + o.bytes, hg + o.hg, hl + o.hl}; }
+};
+
 __global__ void __launch_bounds__(1024) k_vplan(ImgDesc* __restrict__ desc, const dino_view_params* __restrict__ prm,
                                                 int B, int nv, int n_global, int gsize, int lsize, int64_t aws_size,
                                                 ViewPlan* __restrict__ plan) {
-  __shared__ int64_t part[1024];
-  __shared__ int2 hpart[1024];
   const int t = threadIdx.x, N = B * nv;
   for (int b = t; b < B; b += 1024) desc[b].aug_status = 0;
   if (t == 0) plan[N] = ViewPlan{};  // k_hresize's work-item counters (global, local views): hr_chunks, hr_base
-  const int per = (N + 1023) / 1024;
-  int64_t local = 0;
-  int2 hl = make_int2(0, 0);  // k_hresize work items of this thread's global / local views
-  for (int k = 0; k < per; ++k) {
-    int i = t * per + k;
-    if (i < N) {
-      local += plan[i].htmp_off;  // k_vsizes: the view's scratch bytes
-      if ((i % nv) < n_global) hl.x += plan[i].hr_chunks;
-      else hl.y += plan[i].hr_chunks;
-    }
-  }
-  part[t] = local;
-  hpart[t] = hl;
-  __syncthreads();
-  for (int s = 1; s < 1024; s <<= 1) {
-    int64_t v = t >= s ? part[t - s] : 0;
-    int2 hv = t >= s ? hpart[t - s] : make_int2(0, 0);
-    __syncthreads();
-    part[t] += v;
-    hpart[t].x += hv.x;
-    hpart[t].y += hv.y;
-    __syncthreads();
-  }
-  const bool fits = part[1023] <= aws_size;
-  int64_t base = part[t] - local;
-  int2 hb = make_int2(hpart[t].x - hl.x, hpart[t].y - hl.y);
-  for (int k = 0; k < per; ++k) {
-    int i = t * per + k;
-    if (i >= N) continue;
-    ViewPlan vp = plan[i];
-    const int64_t a = vp.htmp_off;
-    vp.ok = vp.ok && fits;
-    vp.htmp_off = base;
-    vp.rcoef_off += base;
-    if ((i % nv) < n_global) {
-      vp.hr_base = hb.x;
-      hb.x += vp.hr_chunks;
-    } else {
-      vp.hr_base = hb.y;
-      hb.y += vp.hr_chunks;
-    }
-    plan[i] = vp;
-    base += a;
-  }
-  if (!fits) {
-    __syncthreads();
-    if (t == 0) {
-      int64_t b = 0;
-      for (int i = 0; i < N; ++i) {
-        ViewPlan& vp = plan[i];
-        const ImgDesc& d = desc[i / nv];
-        int S = (i % nv) < n_global ? gsize : lsize;
-        if (!(d.status == DINO_IMG_OK && params_valid(prm[i], d, S))) continue;
-        int64_t a;
-        int32_t kh, kv;
-        view_sizes(prm[i], 1, &a, &kh, &kv);
-        if (b + a <= aws_size) {
-          vp.ok = 1;
-          vp.htmp_off = b;
-          vp.rcoef_off = b + (kh ? align16((int64_t)prm[i].crop_h * S * 3) : 0);
-          b += a;
-        } else {
-          desc[i / nv].aug_status = DINO_IMG_NO_SPACE;
-        }
-      }
-    }
-  }
+  scan_and_place<ViewSum>(
+      N, aws_size,
+      [&](int i) {  // k_vsizes: htmp_off holds the view's scratch bytes until it is placed
+        const int32_t c = plan[i].hr_chunks;
+        const bool g = (i % nv) < n_global;
+        return ViewSum{plan[i].htmp_off, g ? c : 0, g ? 0 : c};
+      },
+      [&](int i, const ViewSum&, const ViewSum& base, bool placed) {
+        ViewPlan vp = plan[i];
+        vp.ok = vp.ok && placed;
+        vp.htmp_off = base.bytes;
+        vp.rcoef_off += base.bytes;
+        vp.hr_base = (i % nv) < n_global ? base.hg : base.hl;
+        plan[i] = vp;
+      },
+      [&](int i) { desc[i / nv].aug_status = DINO_IMG_NO_SPACE; });
 }
 
 __global__ void __launch_bounds__(256) k_rcoeffs(const ImgDesc* __restrict__ desc, const dino_view_params* __restrict__ prm,
@@ -2820,13 +2784,10 @@ __global__ void __launch_bounds__(256) k_rcoeffs(const ImgDesc* __restrict__ des
   if (!vp.ok) return;
   const dino_view_params p = prm[i];
   const int S = p.out_size;
-  int32_t* base = (int32_t*)(aws + vp.rcoef_off);
-  int32_t* hb = base;                 // [S][2]
-  int32_t* vb = base + 2 * S;         // [S][2]
-  int32_t* ht = base + 4 * S;         // [S][kh]
-  int32_t* vt = ht + (int64_t)S * vp.kh;
-  int4* hx = (int4*)(aws + vp.rcoef_off + align16((int64_t)S * (4 + vp.kh + vp.kv) * 4));
-  uint4* hg = (uint4*)(hx + S);
+  const ViewTables<uint8_t*> T = view_tables(aws + vp.rcoef_off, S, vp.kh, vp.kv);
+  int32_t *hb = (int32_t*)T.hb, *vb = (int32_t*)T.vb, *ht = (int32_t*)T.ht, *vt = (int32_t*)T.vt;
+  int4* hx = (int4*)T.hx;
+  uint4* hg = (uint4*)T.hg;
   for (int x = threadIdx.x; x < S; x += blockDim.x) {
     if (vp.kh) {
       int32_t* k = ht + (int64_t)x * vp.kh;
@@ -3048,10 +3009,10 @@ __device__ __forceinline__ void hresize_item(const ImgDesc* __restrict__ desc, c
     const dino_view_params p = prm[i];
     const ImgDesc& d = desc[b];
     const int S = p.out_size, W = d.width, cw = p.crop_w, kh = vp.kh;
-    const int32_t* gb = (const int32_t*)(aws + vp.rcoef_off);
-    const int32_t* gt = gb + 4 * S;
-    const int4* ghx = (const int4*)(aws + vp.rcoef_off + align16((int64_t)S * (4 + vp.kh + vp.kv) * 4));
-    const uint4* ghg = (const uint4*)(ghx + S);
+    const ViewTables<const uint8_t*> T = view_tables((const uint8_t*)aws + vp.rcoef_off, S, vp.kh, vp.kv);
+    const int32_t *gb = (const int32_t*)T.hb, *gt = (const int32_t*)T.ht;
+    const int4* ghx = (const int4*)T.hx;
+    const uint4* ghg = (const uint4*)T.hg;
     const uint8_t* rgb = ws + d.rgb_off;
     uint8_t* tmp = aws + vp.htmp_off;
     const int64_t cpl = (int64_t)p.crop_h * S;
@@ -3212,8 +3173,7 @@ __device__ __forceinline__ uint32_t vert_apply(const ImgDesc& d, const dino_view
                                                int y0, int nr, const JitterPlan& jp, int hd, Put4 put4, Put1 put1) {
   const int W = d.width;
   const bool need_h = vp.kh != 0, need_v = vp.kv != 0;
-  const int32_t* cbase = (const int32_t*)(aws + vp.rcoef_off);
-  const CoefView cvv{cbase + 2 * S, cbase + 4 * S + (int64_t)S * vp.kh, vp.kv};
+  const CoefView cvv = view_vcoefs(aws + vp.rcoef_off, S, vp.kh, vp.kv);
   const int64_t cpl = (int64_t)p.crop_h * S;
   const uint8_t* htmp = aws + vp.htmp_off;
   uint32_t lsum = 0;
@@ -3828,77 +3788,37 @@ __global__ void __launch_bounds__(kVFinalThreads) k_vfinal(const ImgDesc* __rest
 // image (k_dplan, the ViewPlan slot of view 0): coefficient tables of both axes +
 // the horizontal pass's rows (planar u8 [3][H][ow]).
 // ---------------------------------------------------------------------------
-__device__ void dec_sizes(const ImgDesc& d, int ow, int oh, int64_t* bytes, int32_t* kh, int32_t* kv) {
+// The image's scratch layout (zero bytes when it did not decode) and tap counts.
+__device__ DecScratch<int64_t> dec_layout(const ImgDesc& d, int ow, int oh, int32_t* kh, int32_t* kv) {
   const bool ok = d.status == DINO_IMG_OK;
   *kh = ok && d.width != ow ? resample_ksize(d.width, ow) : 0;
   *kv = ok && d.height != oh ? resample_ksize(d.height, oh) : 0;
-  *bytes = ok ? align16((int64_t)ow * (2 + *kh) * 4) + align16((int64_t)oh * (2 + *kv) * 4) +
-                    (*kh ? align16((int64_t)d.height * ow * 3) : 0)
-              : 0;
+  return ok ? dec_scratch((int64_t)0, ow, oh, d.height, *kh, *kv) : DecScratch<int64_t>{};
 }
+
+struct DecSum {
+  int64_t bytes;
+  __device__ DecSum operator+(const DecSum& o) const { return {bytes + o.bytes}; }
+};
 
 __global__ void __launch_bounds__(1024) k_dplan(ImgDesc* __restrict__ desc, int B, int ow, int oh, int64_t aws_size,
                                                 ViewPlan* __restrict__ plan) {
-  __shared__ int64_t part[1024];
-  const int t = threadIdx.x;
-  const int per = (B + 1023) / 1024;
-  int64_t local = 0;
-  for (int k = 0; k < per; ++k) {
-    const int i = t * per + k;
-    if (i < B) {
-      desc[i].aug_status = 0;
-      int64_t a;
-      int32_t kh, kv;
-      dec_sizes(desc[i], ow, oh, &a, &kh, &kv);
-      local += a;
-    }
-  }
-  part[t] = local;
-  __syncthreads();
-  for (int s = 1; s < 1024; s <<= 1) {
-    const int64_t v = t >= s ? part[t - s] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  const bool fits = part[1023] <= aws_size;
-  int64_t base = part[t] - local;
-  for (int k = 0; k < per; ++k) {
-    const int i = t * per + k;
-    if (i >= B) continue;
-    int64_t a;
-    int32_t kh, kv;
-    dec_sizes(desc[i], ow, oh, &a, &kh, &kv);
-    ViewPlan vp;
-    vp.ok = desc[i].status == DINO_IMG_OK && fits;
-    vp.kh = kh;
-    vp.kv = kv;
-    vp.lsum = 0;
-    vp.rcoef_off = base;
-    vp.htmp_off = base + align16((int64_t)ow * (2 + kh) * 4) + align16((int64_t)oh * (2 + kv) * 4);
-    plan[i] = vp;
-    base += a;
-  }
-  if (!fits) {
-    __syncthreads();
-    if (t == 0) {
-      int64_t b = 0;
-      for (int i = 0; i < B; ++i) {
-        if (desc[i].status != DINO_IMG_OK) continue;
-        int64_t a;
+  for (int b = threadIdx.x; b < B; b += 1024) desc[b].aug_status = 0;
+  scan_and_place<DecSum>(
+      B, aws_size,
+      [&](int i) {
         int32_t kh, kv;
-        dec_sizes(desc[i], ow, oh, &a, &kh, &kv);
-        if (b + a <= aws_size) {
-          plan[i].ok = 1;
-          plan[i].rcoef_off = b;
-          plan[i].htmp_off = b + align16((int64_t)ow * (2 + kh) * 4) + align16((int64_t)oh * (2 + kv) * 4);
-          b += a;
-        } else {
-          desc[i].aug_status = DINO_IMG_NO_SPACE;
-        }
-      }
-    }
-  }
+        return DecSum{dec_layout(desc[i], ow, oh, &kh, &kv).total};
+      },
+      [&](int i, const DecSum&, const DecSum& base, bool placed) {
+        ViewPlan vp{};
+        const DecScratch<int64_t> L = dec_layout(desc[i], ow, oh, &vp.kh, &vp.kv);
+        vp.ok = placed && L.total != 0;
+        vp.rcoef_off = base.bytes;
+        vp.htmp_off = base.bytes + L.htmp;
+        plan[i] = vp;
+      },
+      [&](int i) { desc[i].aug_status = DINO_IMG_NO_SPACE; });
 }
 
 __global__ void __launch_bounds__(256) k_dcoeffs(const ImgDesc* __restrict__ desc, const ViewPlan* __restrict__ plan,
@@ -3907,10 +3827,8 @@ __global__ void __launch_bounds__(256) k_dcoeffs(const ImgDesc* __restrict__ des
   const ViewPlan vp = plan[b];
   if (!vp.ok) return;
   const ImgDesc& d = desc[b];
-  int32_t* hb = (int32_t*)(aws + vp.rcoef_off);
-  int32_t* ht = hb + 2 * ow;
-  int32_t* vb = (int32_t*)(aws + vp.rcoef_off + align16((int64_t)ow * (2 + vp.kh) * 4));
-  int32_t* vt = vb + 2 * oh;
+  const DecScratch<uint8_t*> L = dec_scratch(aws + vp.rcoef_off, ow, oh, d.height, vp.kh, vp.kv);
+  int32_t *hb = (int32_t*)L.hb, *ht = (int32_t*)L.ht, *vb = (int32_t*)L.vb, *vt = (int32_t*)L.vt;
   if (vp.kh)
     for (int x = threadIdx.x; x < ow; x += blockDim.x)
       resample_coeffs_one(d.width, ow, x, vp.kh, &hb[2 * x], &hb[2 * x + 1], ht + (int64_t)x * vp.kh);
@@ -3925,8 +3843,8 @@ __global__ void __launch_bounds__(256) k_dhpass(const ImgDesc* __restrict__ desc
   const ViewPlan vp = plan[b];
   if (!vp.ok || !vp.kh) return;
   const ImgDesc& d = desc[b];
-  const int32_t* hb = (const int32_t*)(aws + vp.rcoef_off);
-  const CoefView cv{hb, hb + 2 * ow, vp.kh};
+  const DecHTables<const uint8_t*> L = dec_htables((const uint8_t*)aws + vp.rcoef_off, ow);
+  const CoefView cv{(const int32_t*)L.hb, (const int32_t*)L.ht, vp.kh};
   const SrcView src{ws + d.rgb_off, (int64_t)d.width * 3, 3, 1};
   uint8_t* tmp = aws + vp.htmp_off;
   const int64_t n = (int64_t)d.height * ow, plane = n;
@@ -3956,8 +3874,8 @@ __global__ void __launch_bounds__(256) k_dvpass(const ImgDesc* __restrict__ desc
       o[e] = (OutT)0;
     return;
   }
-  const int32_t* vb = (const int32_t*)(aws + vp.rcoef_off + align16((int64_t)ow * (2 + vp.kh) * 4));
-  const CoefView cv{vb, vb + 2 * oh, vp.kv};
+  const DecScratch<const uint8_t*> L = dec_scratch(aws + vp.rcoef_off, ow, oh, d.height, vp.kh, vp.kv);
+  const CoefView cv{(const int32_t*)L.vb, (const int32_t*)L.vt, vp.kv};
   const SrcView src = vp.kh ? SrcView{aws + vp.htmp_off, (int64_t)ow, 1, (int64_t)d.height * ow}
                             : SrcView{ws + d.rgb_off, (int64_t)d.width * 3, 3, 1};
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {

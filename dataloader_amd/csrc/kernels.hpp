@@ -6,7 +6,6 @@
 
 namespace dino {
 
-// Per-(image, view) scratch placement, written by k_vplan.
 // Lanes of k_huffman (one workgroup per image).
 constexpr int kHuffThreads = 256;
 // Bits of entropy-coded stream per Huffman work item (kHuffThreads lanes); an image
@@ -16,6 +15,8 @@ constexpr int kHuffThreads = 256;
 #endif
 constexpr int64_t kHuffSegBits = (int64_t)DINO_HUFF_SEG_KBITS * 1024;
 
+// Per-(image, view) scratch placement, written by k_vplan (decode-only: per image, k_dplan).
+// What lies at the two offsets is stated by plan.hpp view_scratch / dec_scratch.
 struct ViewPlan {
   int64_t htmp_off;   // horizontal-pass rows (crop_h x S x 3 u8) in the augment workspace
   int64_t rcoef_off;  // resize coefficient tables

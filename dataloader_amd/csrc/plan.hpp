@@ -8,6 +8,7 @@
 #include "pscan.hpp"
 #include "lscan.hpp"
 #include "resize.hpp"
+#include "augment.hpp"
 
 namespace dino {
 
@@ -94,21 +95,91 @@ DHD ChunkSizes image_chunk_bytes(const ImgDesc& d) {
 // table area: its one scan needs at most 4 DC + 4 AC tables there.
 static_assert(((int64_t)sizeof(HuffTables) - kPTabOff) / (int64_t)sizeof(PTab) >= 8, "switched restart images");
 
-// Horizontal taps in the signed-dot4 layout (k_hresize): per output x an int4
-// {xmin, groups, corr, 0}, then groups of 4 taps as signed base-256 digit planes.
-DHD int64_t hdot_table_bytes(int S, int kh) { return kh ? (int64_t)S * 16 * (1 + (kh + 3) / 4) : 0; }
+// The two scratch layouts of the augment workspace.  These functions state where a table
+// lives: the planners size and place with them and the kernels take their pointers from
+// them.  The one deliberate second spelling is view_vcoefs below (vert_apply's vb and vt,
+// kept as int32 steps for k_vert's sake and held equal to view_tables by
+// tests/test_scratch_layout_cpu.py).  Each is written once over a position type P: a
+// byte pointer into the workspace (kernels: the members are the tables' addresses) or
+// int64_t from 0 (planners, host, tests: byte offsets).
+//
+// A view's coefficient tables, from ViewPlan::rcoef_off: hb[S][2] and vb[S][2] (first
+// source index, tap count per output), ht[S][kh] and vt[S][kv] (int32 taps), then, 16-byte
+// aligned, the horizontal taps in the signed-dot4 layout (k_hresize): hx[S], per output x
+// an int4 {xmin, groups, corr, 0}, and hg[(kh + 3) / 4][S], groups of 4 taps as signed
+// base-256 digit planes (both empty when kh == 0).
+template <typename P>
+struct ViewTables {
+  P hb, vb, ht, vt, hx, hg, end;
+};
+template <typename P>
+DHD ViewTables<P> view_tables(P at, int S, int kh, int kv) {
+  ViewTables<P> t;
+  t.hb = at;
+  t.vb = at + (int64_t)S * 8;
+  t.ht = at + (int64_t)S * 16;
+  t.vt = t.ht + (int64_t)S * kh * 4;
+  t.hx = at + align16((int64_t)S * (4 + kh + kv) * 4);
+  t.hg = t.hx + (kh ? (int64_t)S * 16 : 0);
+  t.end = t.hg + (kh ? (int64_t)S * 16 * ((kh + 3) / 4) : 0);
+  return t;
+}
 
-// Augment scratch of one view: horizontal-pass rows + resize coefficient tables.
-DHD int64_t view_scratch_bytes(int S, int crop_w, int crop_h, int kh, int kv) {
-  const int64_t htmp = kh ? align16((int64_t)crop_h * S * 3) : 0;
-  return htmp + align16((int64_t)S * (4 + kh + kv) * 4) + hdot_table_bytes(S, kh);
+// The vertical pass's tables (vb, vt) of the block at `tab`, for vert_apply (k_vert,
+// k_vfinal).  The same positions as view_tables(tab, ...).vb and .vt (tests/
+// test_scratch_layout_cpu.py holds the two together), spelled as int32 steps: k_vert's
+// time follows the code this compiles to (with view_tables here its prologue grew by five
+// scalar instructions and the kernel ran 7 % slower, 0.254 -> 0.272 ms).
+DHD CoefView view_vcoefs(const uint8_t* tab, int S, int kh, int kv) {
+  const int32_t* cbase = (const int32_t*)tab;
+  return {cbase + 2 * S, cbase + 4 * S + (int64_t)S * kh, kv};
+}
+
+// Augment scratch of one view as byte offsets from ViewPlan::htmp_off: the horizontal
+// pass's rows (planar u8 [3][crop_h][S], only when kh != 0), then the tables above
+// (ViewPlan::rcoef_off is htmp_off + hb).
+struct ViewScratch {
+  int64_t htmp, hb, vb, ht, vt, hx, hg, total;
+};
+DHD ViewScratch view_scratch(int S, int crop_h, int kh, int kv) {
+  const int64_t hb = kh ? align16((int64_t)crop_h * S * 3) : 0;
+  const ViewTables<int64_t> t = view_tables(hb, S, kh, kv);
+  return {0, t.hb, t.vb, t.ht, t.vt, t.hx, t.hg, t.end};
 }
 
 // Upper bound of a view's scratch over every crop of a W x H image (crop sides <= the
 // image's; the tap count grows with the crop side).
 DHD int64_t view_scratch_bound(int S, int W, int H) {
   const int kh = resample_ksize(W > S ? W : S, S), kv = resample_ksize(H > S ? H : S, S);
-  return view_scratch_bytes(S, W, H, kh, kv);
+  return view_scratch(S, H, kh, kv).total;
+}
+
+// Decode-only scratch of one image (k_dplan), from ViewPlan::rcoef_off: hb[ow][2],
+// ht[ow][kh], then vb[oh][2], vt[oh][kv], then the horizontal pass's rows (planar u8
+// [3][H][ow], only when kh != 0; ViewPlan::htmp_off is their position).
+template <typename P>
+struct DecHTables {  // the horizontal pass's part (k_dhpass), which does not depend on oh
+  P hb, ht;
+};
+template <typename P>
+DHD DecHTables<P> dec_htables(P at, int ow) {
+  return {at, at + (int64_t)ow * 8};
+}
+template <typename P>
+struct DecScratch {
+  P hb, ht, vb, vt, htmp, total;
+};
+template <typename P>
+DHD DecScratch<P> dec_scratch(P at, int ow, int oh, int H, int kh, int kv) {
+  const DecHTables<P> h = dec_htables(at, ow);
+  DecScratch<P> t;
+  t.hb = h.hb;
+  t.ht = h.ht;
+  t.vb = at + align16((int64_t)ow * (2 + kh) * 4);
+  t.vt = t.vb + (int64_t)oh * 8;
+  t.htmp = t.vb + align16((int64_t)oh * (2 + kv) * 4);
+  t.total = t.htmp + (kh ? align16((int64_t)H * ow * 3) : 0);
+  return t;
 }
 
 }  // namespace dino

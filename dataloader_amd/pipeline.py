@@ -1432,6 +1432,15 @@ class MI355XPipelineIterator:
         self._pipe.restart_epoch()
 
 
+def resize_scratch_bound(w: int, h: int, ow: int, oh: int) -> int:
+    """Augment-workspace bytes that hold a decoded w x h image's decode-only scratch at
+    ow x oh: an upper bound of csrc/plan.hpp ``dec_scratch(...).total`` (its tap counts are
+    two below these or less, and 64 covers its three 16-byte roundings)."""
+    kh = 2 * (-(-2 * w // ow)) + 3
+    kv = 2 * (-(-2 * h // oh)) + 3
+    return ow * (2 + kh) * 4 + oh * (2 + kv) * 4 + h * ow * 3 + 64
+
+
 class MI355XUserAugPipeline:
     """``UserAugSpec`` on the GPU: the reference's ``CPUUserAugPipeline.run_one_batch``
     (cpu.py:484-500) — decode, resize the shorter side to ``decode_size`` (Pillow BICUBIC,
@@ -1498,12 +1507,7 @@ class MI355XUserAugPipeline:
         if len(shapes) != 1:  # the reference's torch.stack raises on unequal shapes
             raise RuntimeError(f"stack expects each tensor to be equal size, got resized shapes {sorted(shapes)}")
         ow, oh = shapes.pop()
-        aws = 0
-        for st, w, h, _ in info.tolist():
-            if st == 0:
-                kh = 2 * (-(-2 * w // ow)) + 3
-                kv = 2 * (-(-2 * h // oh)) + 3
-                aws += ow * (2 + kh) * 4 + oh * (2 + kv) * 4 + h * ow * 3 + 64
+        aws = sum(resize_scratch_bound(w, h, ow, oh) for st, w, h, _ in info.tolist() if st == 0)
         self._engine.reserve(ws, aws)
         eng = self._engine
         d_bytes = host_buf.to(self.device, non_blocking=True)

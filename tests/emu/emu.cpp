@@ -18,6 +18,7 @@
 #include "../../dataloader_amd/csrc/pixel_ops.hpp"
 #include "../../dataloader_amd/csrc/resize.hpp"
 #include "../../dataloader_amd/csrc/hresize_tile.hpp"
+#include "../../dataloader_amd/csrc/plan.hpp"
 #include "../../dataloader_amd/csrc/augment.hpp"
 #include "../../dataloader_amd/csrc/mask.hpp"
 #include "models.hpp"
@@ -165,6 +166,29 @@ void emu_hresize_tile(int S, int cw, int ch, int kh, int32_t* out) {
 
 // Pillow's tap count for in_size -> out_size (0: the axis is not resampled).
 int emu_resample_ksize(int in_size, int out_size) { return in_size == out_size ? 0 : resample_ksize(in_size, out_size); }
+
+// The scratch layouts of the augment workspace (plan.hpp), as byte offsets:
+// out = {htmp, hb, vb, ht, vt, hx, hg, total} of a view, relative to the view's base.
+void emu_view_scratch(int S, int crop_h, int kh, int kv, int64_t* out) {
+  const ViewScratch L = view_scratch(S, crop_h, kh, kv);
+  const int64_t v[8] = {L.htmp, L.hb, L.vb, L.ht, L.vt, L.hx, L.hg, L.total};
+  memcpy(out, v, sizeof v);
+}
+
+// out = byte offsets {vb, vt} of view_vcoefs' tables from the coefficient block's start.
+void emu_view_vcoefs(int S, int kh, int kv, int64_t* out) {
+  const std::vector<int32_t> block((size_t)S * (4 + kh + kv) + 1);  // a coefficient block's int32 tables
+  const CoefView cv = view_vcoefs((const uint8_t*)block.data(), S, kh, kv);
+  out[0] = (int64_t)(cv.bounds - block.data()) * 4;
+  out[1] = (int64_t)(cv.taps - block.data()) * 4;
+}
+
+// out = {hb, ht, vb, vt, htmp, total} of a decode-only image of height H.
+void emu_dec_scratch(int ow, int oh, int H, int kh, int kv, int64_t* out) {
+  const DecScratch<int64_t> L = dec_scratch((int64_t)0, ow, oh, H, kh, kv);
+  const int64_t v[6] = {L.hb, L.ht, L.vb, L.vt, L.htmp, L.total};
+  memcpy(out, v, sizeof v);
+}
 
 // ---- masks ----------------------------------------------------------------------
 int emu_masks(int H, int W, int target, int minp, int maxp, double la0, double la1, int n, uint32_t* py_state,

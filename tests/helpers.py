@@ -120,6 +120,37 @@ def hresize_tile(lib, S: int, cw: int, ch: int = 1):
     return (*out, (kh + 3) // 4)
 
 
+VIEW_SCRATCH_FIELDS = ("htmp", "hb", "vb", "ht", "vt", "hx", "hg", "total")
+DEC_SCRATCH_FIELDS = ("hb", "ht", "vb", "vt", "htmp", "total")
+
+
+def view_scratch(lib, S: int, crop_h: int, kh: int, kv: int) -> dict[str, int]:
+    """A view's augment scratch layout (plan.hpp view_scratch): byte offsets from its base."""
+    out = (ctypes.c_int64 * 8)()
+    lib.emu_view_scratch(S, crop_h, kh, kv, out)
+    return dict(zip(VIEW_SCRATCH_FIELDS, out))
+
+
+def view_vcoefs(lib, S: int, kh: int, kv: int) -> tuple[int, int]:
+    """Byte offsets (vb, vt) of the vertical pass's tables as vert_apply takes them
+    (plan.hpp view_vcoefs), from the start of the view's coefficient block."""
+    out = (ctypes.c_int64 * 2)()
+    lib.emu_view_vcoefs(S, kh, kv, out)
+    return int(out[0]), int(out[1])
+
+
+def dec_scratch(lib, ow: int, oh: int, H: int, kh: int, kv: int) -> dict[str, int]:
+    """A decode-only image's scratch layout (plan.hpp dec_scratch): byte offsets from its base."""
+    out = (ctypes.c_int64 * 6)()
+    lib.emu_dec_scratch(ow, oh, H, kh, kv, out)
+    return dict(zip(DEC_SCRATCH_FIELDS, out))
+
+
+def dec_scratch_total(lib, w: int, h: int, ow: int, oh: int) -> int:
+    """Exact scratch bytes of a w x h image resized to ow x oh by the decode-only recipe."""
+    return dec_scratch(lib, ow, oh, h, lib.emu_resample_ksize(w, ow), lib.emu_resample_ksize(h, oh))["total"]
+
+
 SWEEP_SIZES = (30, 96, 128, 132, 224, 518, 1024)
 SWEEP_MAX_WIDTH = 2048          # widest raw image of the two large view sizes
 SWEEP_DIRECT_SIZES = (30, 96, 224)  # view sizes whose list goes on to the direct-path pair

@@ -19,7 +19,9 @@ from dataloader_amd import fallback
 from dataloader_amd.config import DINOAugConfig
 from dataloader_amd.engine import IngestEngine, pack_jpegs
 from dataloader_amd.params import OUT_FP32
+from dataloader_amd.pipeline import resize_scratch_bound
 from oracle import cpu_ref
+from tests.helpers import dec_scratch_total
 from tests.test_gpu_resample_sweep import _augment, _engine_for
 
 pytestmark = pytest.mark.gpu
@@ -81,8 +83,7 @@ def test_decode_only_extremes_bit_exact(gpu_device, w, h, ow, oh):
     raw = np.ones(B, np.uint8)
     pinfo, ws, _ = fallback.probe(buf.data_ptr(), off.numpy(), B, 0, raw_mask=raw)
     assert (pinfo[:, 0] == 0).all(), pinfo
-    kh, kv = 2 * (-(-2 * w // ow)) + 3, 2 * (-(-2 * h // oh)) + 3
-    eng.reserve(ws, B * (ow * (2 + kh) * 4 + oh * (2 + kv) * 4 + h * ow * 3 + 64))
+    eng.reserve(ws, B * resize_scratch_bound(w, h, ow, oh))
     info = eng.decode(buf.to(gpu_device), off.to(gpu_device), B, raw_mask=torch.from_numpy(raw).to(gpu_device))
     assert (info.cpu().numpy()[:, 0] == 0).all()
     out = eng.resize_batch(ow, oh, cfg0.mean, cfg0.std, OUT_FP32)
@@ -95,3 +96,47 @@ def test_decode_only_extremes_bit_exact(gpu_device, w, h, ow, oh):
         ref = cpu_ref.to_tensor_normalized(Image.fromarray(im, "RGB").resize((ow, oh), Image.BICUBIC),
                                            cfg0.mean, cfg0.std, torch.float32)
         assert torch.equal(ref, out[b]), (b, int((ref != out[b]).sum()))
+
+
+def test_decode_only_greedy_no_cascade(gpu_device, emu):
+    """k_dplan's greedy branch: a 256 x 8192 image needs 8192 x 64 x 3 = 1 572 864 bytes of
+    horizontal-pass rows, more than the engine's default augment workspace (4 x (32 x 3 x 1024
+    + 256 KiB) = 1 441 792 bytes), so the batch does not fit.  The tall image alone is
+    reported DINO_IMG_NO_SPACE (3) and comes out as zeros; the small images around it (under
+    40 KB each) are placed and resized bit for bit.  With the workspace reserved to the exact
+    sum of the images' dec_scratch totals, the batch fits and all four are bit-exact."""
+    OW = OH = 64
+    rng = np.random.default_rng(64)
+    shapes = [(96, 64), (256, 8192), (96, 64), (64, 96)]  # (w, h)
+    images = [rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8) for w, h in shapes]
+    B = len(images)
+    cfg0 = DINOAugConfig()
+    refs = [cpu_ref.to_tensor_normalized(Image.fromarray(im, "RGB").resize((OW, OH), Image.BICUBIC),
+                                         cfg0.mean, cfg0.std, torch.float32) for im in images]
+    eng = IngestEngine(gpu_device, max_batch=B, max_views=1, max_crop_size=32)
+    buf, off = pack_jpegs([fallback.raw_container(im) for im in images], pin=False)
+    raw = np.ones(B, np.uint8)
+    pinfo, ws, _ = fallback.probe(buf.data_ptr(), off.numpy(), B, 0, raw_mask=raw)
+    assert (pinfo[:, 0] == 0).all(), pinfo
+    eng.reserve(ws, 0)  # the augment workspace keeps its default size
+    assert eng.workspace_sizes()[1] == 1441792
+    info = eng.decode(buf.to(gpu_device), off.to(gpu_device), B, raw_mask=torch.from_numpy(raw).to(gpu_device))
+    assert (info.cpu().numpy()[:, 0] == 0).all()
+
+    def run():
+        out = eng.resize_batch(OW, OH, cfg0.mean, cfg0.std, OUT_FP32)
+        st = eng.batch_info(torch.empty(B, 4, dtype=torch.int32, device=gpu_device))
+        torch.cuda.synchronize()
+        return out.cpu(), st.cpu().numpy()[:, 0].tolist()
+
+    out, status = run()
+    assert status == [0, 3, 0, 0], status
+    assert not out[1].any()
+    for b in (0, 2, 3):
+        assert torch.equal(refs[b], out[b]), (b, int((refs[b] != out[b]).sum()))
+    eng.reserve(ws, sum(dec_scratch_total(emu, w, h, OW, OH) for w, h in shapes))
+    out, status = run()
+    eng.close()
+    assert status == [0, 0, 0, 0], status
+    for b in range(B):
+        assert torch.equal(refs[b], out[b]), (b, int((refs[b] != out[b]).sum()))
