@@ -93,6 +93,8 @@ def load() -> ctypes.CDLL:
         "dino_debug_region": (i32, [vp, i32, i32, vp, i64, vp]),
         "dino_set_timing": (i32, [vp, i32]),
         "dino_ctx_set_prog_decoder": (i32, [vp, i32]),
+        "dino_ctx_set_resample_filter": (i32, [vp, i32]),
+        "dino_resample_coeffs_host": (i32, [i32, i32, i32, i32, i32, vp, vp, vp]),
         "dino_kernel_times": (i32, [vp, vp, vp, i32]),
         "dino_tar_index": (i32, [vp, i64, vp, i64, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
         "dino_tar_index_fd": (i32, [i32, i64, i64, vp, i64, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
@@ -133,4 +135,5 @@ def exported_symbols() -> list[str]:
             "dino_feed_create", "dino_feed_destroy", "dino_feed_push", "dino_feed_end_epoch", "dino_feed_set_cfg",
             "dino_feed_set_shard_wait", "dino_feed_set_shuffle", "dino_feed_set_epoch",
             "dino_feed_next", "dino_feed_copy", "dino_feed_release", "dino_feed_reset", "dino_feed_stats",
-            "dino_feed_last_error", "dino_stream_create", "dino_stream_destroy"]
+            "dino_feed_last_error", "dino_stream_create", "dino_stream_destroy",
+            "dino_ctx_set_resample_filter", "dino_resample_coeffs_host"]

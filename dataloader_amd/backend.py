@@ -30,6 +30,7 @@ from typing import TYPE_CHECKING, Any
 import torch
 
 from . import _lib
+from .params import resample_filter_code
 from .pipeline import MI355XAugPipeline, MI355XPipelineIterator
 
 if TYPE_CHECKING:
@@ -120,7 +121,16 @@ class MI355XBackend:
 
     def __init__(self, max_image_dim: int = 0, workspace_bytes: int = 0, max_in_flight: int = 3,
                  hbm_fraction: float = 0.15, host_workers: int | None = None, multiscan_route: str = "side",
-                 side_ahead: int | None = None) -> None:
+                 side_ahead: int | None = None, resample_filter: str | None = None) -> None:
+        # Pillow filter of every resize: None = bicubic everywhere (CPUBackend parity, which
+        # ignores EvalAugSpec.interpolation too); a filter's name applies to every recipe;
+        # "spec" honours EvalAugSpec.interpolation as the reference's GPU peer does
+        # (pipeline.py:539) and means bicubic for the other specs
+        if resample_filter is not None and resample_filter != "spec":
+            if not isinstance(resample_filter, str):
+                raise ValueError(f"resample_filter must be a filter's name, 'spec' or None, not {resample_filter!r}")
+            resample_filter_code(resample_filter)  # ValueError on an unknown name
+        self._resample_filter = resample_filter
         self._max_image_dim = max_image_dim
         self._workspace_bytes = workspace_bytes
         self._max_in_flight = max(1, int(max_in_flight))
@@ -163,6 +173,16 @@ class MI355XBackend:
             while want > 1 and MI355XAugPipeline.pulled_bound(depth, self.PREFETCH, want) + 1 > cap:
                 want -= 1
         return max(1, int(want))
+
+    def spec_filter(self, aug_spec: Any) -> str | None:
+        """The filter a pipeline for ``aug_spec`` is built with (None: bicubic)."""
+        if self._resample_filter != "spec":
+            return self._resample_filter
+        if type(aug_spec).__name__ != "EvalAugSpec":
+            return None
+        name = getattr(aug_spec, "interpolation", "bicubic")
+        resample_filter_code(name)  # ValueError on a name Pillow does not have
+        return name
 
     def queue_depth(self, pipeline_cfg: Any, batch_size: int, n_views: int = 10, max_crop: int = 224) -> int:
         """Batches in flight for ``pipeline_cfg.gpu_queue``, capped by ``max_in_flight`` and by
@@ -220,7 +240,7 @@ class MI355XBackend:
             return MI355XUserAugPipeline(source, aug_spec, getattr(source, "_batch_size", 1),
                                          out_dtype=pipeline_cfg.output_dtype, device=pipeline_cfg.device_id,
                                          max_image_dim=self._max_image_dim, workspace_bytes=self._workspace_bytes,
-                                         norm=norm)
+                                         norm=norm, resample_filter=self.spec_filter(aug_spec))
         if _is_dinov2_spec(aug_spec):
             aug_cfg = aug_spec.aug_cfg
             names = None
@@ -262,6 +282,7 @@ class MI355XBackend:
             start_host_pool=True,
             multiscan_route=self._multiscan_route,
             side_ahead=self.side_look_ahead(pipeline_cfg, source, depth),
+            resample_filter=self.spec_filter(aug_spec),
         )
 
     def build_pipeline_iterator(self, pipeline: Any, aug_spec: Any, output_map: list[str],

@@ -62,6 +62,7 @@ struct dino_ctx {
   int32_t last_batch = -1;
   hipStream_t ws_stream = nullptr;  // stream of the last dino_reserve (the workspaces' release order)
   LaunchGeom geom{};
+  int32_t filter = kBicubic;  // dino_ctx_set_resample_filter: read at each augment / resize launch
   KernelTimer* timer = nullptr;
   KernelTimer* tm() { return timer && timer->enabled ? timer : nullptr; }
 };
@@ -219,7 +220,7 @@ int dino_augment(dino_ctx* c, const dino_aug_config* cfg, const dino_view_params
     return fail(DINO_EINVAL, "dino_augment: dino_set_norm covers %s%lld images, fewer than the batch", "", c->norm_n);
   hipStream_t s = (hipStream_t)stream;
   AugmentArgs a{c->d_desc, c->last_batch, d_params, c->d_plan, c->d_ws, c->d_aws, c->aws_size, c->d_gcrop, {}, *cfg,
-                c->d_norm, c->geom.grid_hr};
+                c->d_norm, c->geom.grid_hr, c->filter};
   for (int v = 0; v < nv; ++v) {
     if (!d_views[v]) return fail(DINO_EINVAL, "dino_augment: null output pointer for view %s%lld", "", v);
     a.views.p[v] = d_views[v];
@@ -269,7 +270,7 @@ int dino_resize_batch(dino_ctx* c, int32_t out_w, int32_t out_h, const float* me
     return fail(DINO_EINVAL, "dino_resize_batch: dino_set_norm covers %s%lld images, fewer than the batch", "",
                 c->norm_n);
   DecodeOnlyArgs a{c->d_desc, c->last_batch, out_w, out_h, out_dtype, c->d_plan, c->d_ws, c->d_aws, c->aws_size,
-                   {mean[0], mean[1], mean[2]}, {stdv[0], stdv[1], stdv[2]}, c->d_norm, d_out};
+                   {mean[0], mean[1], mean[2]}, {stdv[0], stdv[1], stdv[2]}, c->d_norm, d_out, c->filter};
   hipError_t e = launch_decode_only(a, (hipStream_t)stream);
   return e == hipSuccess ? DINO_OK : hip_fail(e, "dino_resize_batch");
 }
@@ -547,6 +548,30 @@ int dino_ctx_set_prog_decoder(dino_ctx* c, int32_t decoder) {
   return DINO_OK;
 }
 
+int dino_ctx_set_resample_filter(dino_ctx* c, int32_t filter) {
+  if (!c) return fail(DINO_EINVAL, "dino_ctx_set_resample_filter: null ctx%s%lld");
+  if (filter < 0 || filter >= kNumResampleFilters)
+    return fail(DINO_EINVAL, "dino_ctx_set_resample_filter: unknown filter%s %lld", "", (long long)filter);
+  c->filter = filter;
+  return DINO_OK;
+}
+
+int dino_resample_coeffs_host(int32_t filter, int32_t in_size, int32_t out_size, int32_t x0, int32_t n, int32_t* ksize,
+                              int32_t* bounds, int32_t* taps) {
+  if (filter < 0 || filter >= kNumResampleFilters)
+    return fail(DINO_EINVAL, "dino_resample_coeffs_host: unknown filter%s %lld", "", (long long)filter);
+  if (!ksize || in_size < 1 || out_size < 1 || in_size > 65536 || out_size > 65536)
+    return fail(DINO_EINVAL, "dino_resample_coeffs_host: bad sizes%s%lld");
+  const int k = resample_ksize(in_size, out_size, filter);
+  *ksize = k;
+  if (!taps) return DINO_OK;
+  if (!bounds || x0 < 0 || n < 0 || (int64_t)x0 + n > out_size)
+    return fail(DINO_EINVAL, "dino_resample_coeffs_host: bad output range%s%lld");
+  for (int32_t i = 0; i < n; ++i)
+    resample_coeffs_one(in_size, out_size, x0 + i, k, &bounds[2 * i], &bounds[2 * i + 1], taps + (int64_t)i * k, filter);
+  return DINO_OK;
+}
+
 int dino_set_timing(dino_ctx* c, int32_t enable) {
   if (!c) return fail(DINO_EINVAL, "dino_set_timing: null ctx%s%lld");
   if (!c->timer) c->timer = new KernelTimer();
@@ -580,6 +605,12 @@ int dino_debug_region(dino_ctx* c, int32_t index, int32_t region, void* d_dst, i
   if (e != hipSuccess) return hip_fail(e, "dino_debug_region");
   const void* src = nullptr;
   int64_t n = 0;
+  ViewPlan vp{};
+  if (region == 7) {  // (one plan record per image after dino_resize_batch)
+    e = hipMemcpyAsync(&vp, c->d_plan + index, sizeof(ViewPlan), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "dino_debug_region");
+  }
   switch (region) {
     case 0: src = c->d_desc + index; n = sizeof(ImgDesc); break;
     case 1: src = c->d_ws + d.ent_off; n = d.ent_len; break;
@@ -593,6 +624,12 @@ int dino_debug_region(dino_ctx* c, int32_t index, int32_t region, void* d_dst, i
     case 6:  // kind 1: the scan list header (PHdr: levels, lane-decoder flag and slots)
       src = c->d_ws + d.htab_off;
       n = d.kind == 1 ? (int64_t)sizeof(PHdr) : 0;
+      break;
+    case 7:  // the coefficient tables of the image's last dino_resize_batch (plan.hpp dec_scratch)
+      if (!vp.ok || vp.rcoef_off < 0 || vp.htmp_off < vp.rcoef_off || vp.htmp_off > c->aws_size)
+        return fail(DINO_EINVAL, "dino_debug_region: image %s%lld has no resize tables", "", index);
+      src = c->d_aws + vp.rcoef_off;
+      n = vp.htmp_off - vp.rcoef_off;
       break;
     default: return fail(DINO_EINVAL, "dino_debug_region: region %s%lld", "", region);
   }

@@ -83,10 +83,27 @@ struct ImgDesc {
   int32_t aug_status;      // DINO_IMG_NO_SPACE when k_vplan could not place one of its views
 };
 
+// Resampling filter of a context (include/dino_ingest.h DINO_FILTER_*, Pillow's names).
+// 0 is BICUBIC, so that every zero-initialised structure means the one filter there was.
+enum ResampleFilter : int32_t { kBicubic = 0, kBilinear = 1, kBox = 2, kHamming = 3, kLanczos = 4 };
+constexpr int kNumResampleFilters = 5;
+
+// Twice the filter's support (Resample.c: BOX 0.5, BILINEAR and HAMMING 1, BICUBIC 2, LANCZOS 3).
+DHD int resample_support2(int filter) {
+  switch (filter) {
+    case kBox: return 1;
+    case kBilinear:
+    case kHamming: return 2;
+    case kLanczos: return 6;
+    default: return 4;
+  }
+}
+
 // Bytes of resize-coefficient scratch reserved per view: bounds + int32 taps, both axes.
-DHD int64_t rcoef_stride_bytes(int out_size, int max_dim) {
-  // ksize = 2*ceil(support*scale)+1 with support 2 and scale <= max_dim/out
-  int k = 2 * ((2 * max_dim + out_size - 1) / out_size) + 3;
+DHD int64_t rcoef_stride_bytes(int out_size, int max_dim, int filter = kBicubic) {
+  // ksize = 2*ceil(support*scale)+1 with scale <= max_dim/out (support 2: bicubic)
+  const int s2 = resample_support2(filter);
+  int k = 2 * (int)(((int64_t)s2 * max_dim + 2 * out_size - 1) / (2 * out_size)) + 3;
   return (int64_t)2 * out_size * (k + 2) * 4;
 }
 

@@ -11,7 +11,7 @@
 // Augment half (per view):
 //   k_params    1 lane / view       Philox draw of the view record (optional)
 //   k_vplan     1 workgroup         per-view scratch offsets
-//   k_rcoeffs   lanes over outputs  Pillow bicubic coefficient tables (both axes)
+//   k_rcoeffs   lanes over outputs  Pillow coefficient tables of the context's filter (both axes)
 //   k_hresize   lanes over pixels   horizontal pass (crop rows -> S columns, u8)
 //   k_augment   1 workgroup / view  vertical pass -> LDS planes -> jitter -> gray
 //                                   -> blur + solarize + normalize -> NCHW output
@@ -2717,7 +2717,7 @@ __device__ bool params_valid(const dino_view_params& p, const ImgDesc& d, int S)
 // the size and rcoef_off the offset of the coefficient tables inside it until k_vplan
 // places the view), so that the single-workgroup scan only reads packed records.
 __global__ void __launch_bounds__(256) k_vsizes(const ImgDesc* __restrict__ desc, const dino_view_params* __restrict__ prm,
-                                                int B, int nv, int n_global, int gsize, int lsize,
+                                                int B, int nv, int n_global, int gsize, int lsize, int filter,
                                                 ViewPlan* __restrict__ plan) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * nv) return;
@@ -2725,8 +2725,8 @@ __global__ void __launch_bounds__(256) k_vsizes(const ImgDesc* __restrict__ desc
   const int S = (i % nv) < n_global ? gsize : lsize;
   const int ok = d.status == DINO_IMG_OK && params_valid(prm[i], d, S);
   const dino_view_params& p = prm[i];
-  const int32_t kh = ok && p.crop_w != view_rw(p) ? resample_ksize(p.crop_w, view_rw(p)) : 0;
-  const int32_t kv = ok && p.crop_h != view_rh(p) ? resample_ksize(p.crop_h, view_rh(p)) : 0;
+  const int32_t kh = ok && p.crop_w != view_rw(p) ? resample_ksize(p.crop_w, view_rw(p), filter) : 0;
+  const int32_t kv = ok && p.crop_h != view_rh(p) ? resample_ksize(p.crop_h, view_rh(p), filter) : 0;
   const ViewScratch L = view_scratch(S, p.crop_h, kh, kv);
   ViewPlan vp;
   vp.ok = ok;
@@ -2777,7 +2777,7 @@ __global__ void __launch_bounds__(1024) k_vplan(ImgDesc* __restrict__ desc, cons
 }
 
 __global__ void __launch_bounds__(256) k_rcoeffs(const ImgDesc* __restrict__ desc, const dino_view_params* __restrict__ prm,
-                                                 const ViewPlan* __restrict__ plan, int nv, int v0,
+                                                 const ViewPlan* __restrict__ plan, int nv, int v0, int filter,
                                                  const uint8_t* __restrict__ ws, uint8_t* __restrict__ aws) {
   const int i = blockIdx.y * nv + v0 + blockIdx.x;
   const ViewPlan vp = plan[i];
@@ -2791,10 +2791,11 @@ __global__ void __launch_bounds__(256) k_rcoeffs(const ImgDesc* __restrict__ des
   for (int x = threadIdx.x; x < S; x += blockDim.x) {
     if (vp.kh) {
       int32_t* k = ht + (int64_t)x * vp.kh;
-      resample_coeffs_one(p.crop_w, view_rw(p), p.out_x + x, vp.kh, &hb[2 * x], &hb[2 * x + 1], k);
+      resample_coeffs_one(p.crop_w, view_rw(p), p.out_x + x, vp.kh, &hb[2 * x], &hb[2 * x + 1], k, filter);
       // sum_t p_t k_t = sum_t (p_t - 128) k_t + 128 sum_t k_t, and k_t = D0 + 256 D1 + 65536 D2
-      // with signed digits D in [-128, 127] (exact for |k| < 2^23 - 2^15; normalised bicubic
-      // taps stay below 1.1 x 2^22): three v_dot4 products per 4 taps
+      // with signed digits D in [-128, 127] (exact for -2^23 - 2^15 <= k < 2^23 - 2^15 = 1.992 x
+      // 2^22; the largest tap of any filter is LANCZOS's 1.2851 x 2^22, resize.hpp tap_mad): three
+      // v_dot4 products per 4 taps
       const int cnt = hb[2 * x + 1], ng = (cnt + 3) / 4;
       int32_t ksum = 0;
       for (int g = 0; g < ng; ++g) {
@@ -2818,7 +2819,8 @@ __global__ void __launch_bounds__(256) k_rcoeffs(const ImgDesc* __restrict__ des
       hx[x] = make_int4(hb[2 * x], ng, 128 * ksum + (1 << (kPrecisionBits - 1)), 0);
     }
     if (vp.kv)
-      resample_coeffs_one(p.crop_h, view_rh(p), p.out_y + x, vp.kv, &vb[2 * x], &vb[2 * x + 1], vt + (int64_t)x * vp.kv);
+      resample_coeffs_one(p.crop_h, view_rh(p), p.out_y + x, vp.kv, &vb[2 * x], &vb[2 * x + 1], vt + (int64_t)x * vp.kv,
+                          filter);
   }
   if (!resample_vfirst(p.crop_w, p.crop_h, view_rh(p), vp.kh)) return;
   // Vertical pass first (resample_vfirst: a crop over 100 times as high as wide, which no
@@ -3783,16 +3785,16 @@ __global__ void __launch_bounds__(kVFinalThreads) k_vfinal(const ImgDesc* __rest
 // ---------------------------------------------------------------------------
 // Decode-only recipe (reference CPUUserAugPipeline, cpu.py:484-500; DALI
 // _build_decode_only_pipeline, pipeline.py:693-756): every image of the batch
-// resampled whole (Pillow BICUBIC, horizontal pass then vertical, each only when
+// resampled whole (Pillow BICUBIC or the context's filter, horizontal pass then vertical, each only when
 // that axis changes size) to ow x oh, normalised and cast, NCHW.  Scratch per
 // image (k_dplan, the ViewPlan slot of view 0): coefficient tables of both axes +
 // the horizontal pass's rows (planar u8 [3][H][ow]).
 // ---------------------------------------------------------------------------
 // The image's scratch layout (zero bytes when it did not decode) and tap counts.
-__device__ DecScratch<int64_t> dec_layout(const ImgDesc& d, int ow, int oh, int32_t* kh, int32_t* kv) {
+__device__ DecScratch<int64_t> dec_layout(const ImgDesc& d, int ow, int oh, int filter, int32_t* kh, int32_t* kv) {
   const bool ok = d.status == DINO_IMG_OK;
-  *kh = ok && d.width != ow ? resample_ksize(d.width, ow) : 0;
-  *kv = ok && d.height != oh ? resample_ksize(d.height, oh) : 0;
+  *kh = ok && d.width != ow ? resample_ksize(d.width, ow, filter) : 0;
+  *kv = ok && d.height != oh ? resample_ksize(d.height, oh, filter) : 0;
   return ok ? dec_scratch((int64_t)0, ow, oh, d.height, *kh, *kv) : DecScratch<int64_t>{};
 }
 
@@ -3801,18 +3803,18 @@ struct DecSum {
   __device__ DecSum operator+(const DecSum& o) const { return {bytes + o.bytes}; }
 };
 
-__global__ void __launch_bounds__(1024) k_dplan(ImgDesc* __restrict__ desc, int B, int ow, int oh, int64_t aws_size,
-                                                ViewPlan* __restrict__ plan) {
+__global__ void __launch_bounds__(1024) k_dplan(ImgDesc* __restrict__ desc, int B, int ow, int oh, int filter,
+                                                int64_t aws_size, ViewPlan* __restrict__ plan) {
   for (int b = threadIdx.x; b < B; b += 1024) desc[b].aug_status = 0;
   scan_and_place<DecSum>(
       B, aws_size,
       [&](int i) {
         int32_t kh, kv;
-        return DecSum{dec_layout(desc[i], ow, oh, &kh, &kv).total};
+        return DecSum{dec_layout(desc[i], ow, oh, filter, &kh, &kv).total};
       },
       [&](int i, const DecSum&, const DecSum& base, bool placed) {
         ViewPlan vp{};
-        const DecScratch<int64_t> L = dec_layout(desc[i], ow, oh, &vp.kh, &vp.kv);
+        const DecScratch<int64_t> L = dec_layout(desc[i], ow, oh, filter, &vp.kh, &vp.kv);
         vp.ok = placed && L.total != 0;
         vp.rcoef_off = base.bytes;
         vp.htmp_off = base.bytes + L.htmp;
@@ -3822,7 +3824,7 @@ __global__ void __launch_bounds__(1024) k_dplan(ImgDesc* __restrict__ desc, int 
 }
 
 __global__ void __launch_bounds__(256) k_dcoeffs(const ImgDesc* __restrict__ desc, const ViewPlan* __restrict__ plan,
-                                                 int ow, int oh, uint8_t* __restrict__ aws) {
+                                                 int ow, int oh, int filter, uint8_t* __restrict__ aws) {
   const int b = blockIdx.x;
   const ViewPlan vp = plan[b];
   if (!vp.ok) return;
@@ -3831,10 +3833,10 @@ __global__ void __launch_bounds__(256) k_dcoeffs(const ImgDesc* __restrict__ des
   int32_t *hb = (int32_t*)L.hb, *ht = (int32_t*)L.ht, *vb = (int32_t*)L.vb, *vt = (int32_t*)L.vt;
   if (vp.kh)
     for (int x = threadIdx.x; x < ow; x += blockDim.x)
-      resample_coeffs_one(d.width, ow, x, vp.kh, &hb[2 * x], &hb[2 * x + 1], ht + (int64_t)x * vp.kh);
+      resample_coeffs_one(d.width, ow, x, vp.kh, &hb[2 * x], &hb[2 * x + 1], ht + (int64_t)x * vp.kh, filter);
   if (vp.kv)
     for (int y = threadIdx.x; y < oh; y += blockDim.x)
-      resample_coeffs_one(d.height, oh, y, vp.kv, &vb[2 * y], &vb[2 * y + 1], vt + (int64_t)y * vp.kv);
+      resample_coeffs_one(d.height, oh, y, vp.kv, &vb[2 * y], &vb[2 * y + 1], vt + (int64_t)y * vp.kv, filter);
 }
 
 __global__ void __launch_bounds__(256) k_dhpass(const ImgDesc* __restrict__ desc, const ViewPlan* __restrict__ plan,
@@ -3899,8 +3901,8 @@ static hipError_t launch_dec_out(const DecodeOnlyArgs& a, hipStream_t s) {
 
 hipError_t launch_decode_only(const DecodeOnlyArgs& a, hipStream_t s) {
   if (a.batch <= 0) return hipSuccess;
-  k_dplan<<<1, 1024, 0, s>>>(a.desc, a.batch, a.ow, a.oh, a.aws_size, a.plan);
-  k_dcoeffs<<<a.batch, 256, 0, s>>>(a.desc, a.plan, a.ow, a.oh, a.aws);
+  k_dplan<<<1, 1024, 0, s>>>(a.desc, a.batch, a.ow, a.oh, a.filter, a.aws_size, a.plan);
+  k_dcoeffs<<<a.batch, 256, 0, s>>>(a.desc, a.plan, a.ow, a.oh, a.filter, a.aws);
   k_dhpass<<<dim3(64, a.batch), 256, 0, s>>>(a.desc, a.plan, a.ow, a.ws, a.aws);
   switch (a.out_dtype) {
     case DINO_OUT_FP32: return launch_dec_out<float>(a, s);
@@ -4174,7 +4176,7 @@ static hipError_t launch_augment_class(const AugmentArgs& a, int v0, int nvc, in
   const int kfin = v0 == 0 ? kKFinalGlobal : kKFinalLocal;
   const int kvert = v0 == 0 ? kKVertGlobal : kKVertLocal;
   const int rc_threads = S < 256 ? (S + 63) / 64 * 64 : 256;  // one lane per output column
-  TIMED(tm, kKRcoeffs, s, (k_rcoeffs<<<dim3(nvc, B), rc_threads, 0, s>>>(a.desc, a.params, a.plan, nv, v0, a.ws, a.aws)));
+  TIMED(tm, kKRcoeffs, s, (k_rcoeffs<<<dim3(nvc, B), rc_threads, 0, s>>>(a.desc, a.params, a.plan, nv, v0, a.filter, a.ws, a.aws)));
   TIMED(tm, kKHresize, s,
         (k_hresize<<<a.grid_hr, 256, kHresizeLds, s>>>(a.desc, a.params, a.plan, nv, v0, nvc, B, a.ws, a.aws)));
   if (S <= kVFinalMaxS) {  // small views: vertical pass and epilogue fused, the view stays in LDS
@@ -4205,7 +4207,7 @@ hipError_t launch_augment(const AugmentArgs& a, hipStream_t s, KernelTimer* tm) 
   const int B = a.batch, nv = a.cfg.n_global + a.cfg.n_local;
   if (B <= 0 || nv <= 0) return hipSuccess;
   TIMED(tm, kKVplan, s, (k_vsizes<<<(B * nv + 255) / 256, 256, 0, s>>>(a.desc, a.params, B, nv, a.cfg.n_global,
-                                                                       a.cfg.global_size, a.cfg.local_size, a.plan)));
+                                                                       a.cfg.global_size, a.cfg.local_size, a.filter, a.plan)));
   TIMED(tm, kKVplan, s, (k_vplan<<<1, 1024, 0, s>>>(a.desc, a.params, B, nv, a.cfg.n_global, a.cfg.global_size,
                                                      a.cfg.local_size, a.aws_size, a.plan)));
   switch (a.cfg.out_dtype) {

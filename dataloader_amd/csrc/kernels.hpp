@@ -111,6 +111,7 @@ struct AugmentArgs {
   dino_aug_config cfg;
   const float* norm;       // per-image {mean[3], std[3]} ([0, 1] scale), nullable -> cfg.mean / cfg.std
   int32_t grid_hr;         // LaunchGeom::grid_hr
+  int32_t filter;          // ResampleFilter of every view's resample (0: BICUBIC)
 };
 
 // Decode-only recipe (dino_resize_batch).
@@ -124,6 +125,7 @@ struct DecodeOnlyArgs {
   float mean[3], std[3];
   const float* norm;
   void* out;
+  int32_t filter;  // ResampleFilter (0: BICUBIC)
 };
 
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm = nullptr);

@@ -148,11 +148,20 @@ DHD ViewScratch view_scratch(int S, int crop_h, int kh, int kv) {
 }
 
 // Upper bound of a view's scratch over every crop of a W x H image (crop sides <= the
-// image's; the tap count grows with the crop side).
-DHD int64_t view_scratch_bound(int S, int W, int H) {
-  const int kh = resample_ksize(W > S ? W : S, S), kv = resample_ksize(H > S ? H : S, S);
+// image's; the tap count grows with the crop side).  The probes state it for BICUBIC; for a
+// context with another filter the caller multiplies it by resample_bound_scale.
+DHD int64_t view_scratch_bound(int S, int W, int H, int filter = kBicubic) {
+  const int kh = resample_ksize(W > S ? W : S, S, filter), kv = resample_ksize(H > S ? H : S, S, filter);
   return view_scratch(S, H, kh, kv).total;
 }
+
+// Factor by which a filter's scratch can exceed BICUBIC's for the same sizes: the support
+// ratio rounded up.  With u = ceil(2 fs), BICUBIC has k = 2 u + 1 taps and LANCZOS
+// 2 ceil(3 fs) + 1 <= 2 (2 u) + 1 < 2 k, and its groups of 4 taps floor((2 k + 3) / 4) <=
+// 2 floor((k + 3) / 4) for odd k >= 5; the rows of the horizontal pass do not depend on the
+// filter, and every table's size is linear in its tap or group count plus a constant.  The
+// filters of support <= 2 never have more taps than BICUBIC.
+DHD int resample_bound_scale(int filter) { return (resample_support2(filter) + 3) / 4; }
 
 // Decode-only scratch of one image (k_dplan), from ViewPlan::rcoef_off: hb[ow][2],
 // ht[ow][kh], then vb[oh][2], vt[oh][kv], then the horizontal pass's rows (planar u8

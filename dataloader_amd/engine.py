@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .params import OUT_BF16, OUT_FP8_E4M3, OUT_FP32, VIEW_PARAMS_DTYPE, DinoLimits
+from .params import (OUT_BF16, OUT_FP8_E4M3, OUT_FP32, VIEW_PARAMS_DTYPE, DinoLimits, resample_bound_scale,
+                     resample_filter_code)
 
 _TORCH_OUT = {OUT_BF16: torch.bfloat16, OUT_FP32: torch.float32, OUT_FP8_E4M3: torch.float8_e4m3fn}
 
@@ -64,6 +65,7 @@ class IngestEngine:
         self.last_batch = 0
         self.stream = stream  # None: launch on torch's current stream
         self.prog_lanes: bool | None = None  # set_prog_decoder's choice (None: the library default)
+        self.resample_filter = 0  # set_resample_filter's choice (DINO_FILTER_*; 0: bicubic)
 
     def _s(self) -> ctypes.c_void_p:
         return _stream_handle(self.device, self.stream)
@@ -127,6 +129,15 @@ class IngestEngine:
         64 images per wave, for large pools decoded well ahead) or the wave decoder."""
         _lib.check(self.lib.dino_ctx_set_prog_decoder(self._ctx, int(bool(lanes))), "dino_ctx_set_prog_decoder")
         self.prog_lanes = bool(lanes)
+
+    def set_resample_filter(self, f) -> None:
+        """Resample this context's views and decode-only resizes with Pillow's filter ``f``
+        ("bicubic", "bilinear", "box", "hamming", "lanczos", a ``DINO_FILTER_*`` code, or None
+        for bicubic) from the next call on (``dino_ctx_set_resample_filter``).  ``reserve``
+        scales the augment workspace it is asked for accordingly."""
+        code = resample_filter_code(f)
+        _lib.check(self.lib.dino_ctx_set_resample_filter(self._ctx, code), "dino_ctx_set_resample_filter")
+        self.resample_filter = code
 
     def set_timing(self, enable: bool) -> None:
         _lib.check(self.lib.dino_set_timing(self._ctx, int(enable)), "dino_set_timing")
@@ -210,7 +221,9 @@ class IngestEngine:
     def reserve(self, ws_bytes: int, aws_bytes: int) -> bool:
         """Grow the decode / augment workspaces to at least these sizes (``dino_reserve``),
         stream-ordered on this engine's stream (no other stream of the device waits).
-        Returns True when it had to reallocate."""
+        Returns True when it had to reallocate.  ``aws_bytes`` is a bound for bicubic (the
+        probes', ``dino_augment_need``'s); it is scaled here to this context's filter."""
+        aws_bytes = int(aws_bytes) * resample_bound_scale(self.resample_filter)
         cur_ws, cur_aws = self.workspace_sizes()
         if ws_bytes <= cur_ws and aws_bytes <= cur_aws:
             return False

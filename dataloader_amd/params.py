@@ -29,6 +29,29 @@ RECIPE_DINOV2, RECIPE_LEJEPA, RECIPE_EVAL = 0, 1, 2
 
 OUT_BF16, OUT_FP32, OUT_FP8_E4M3 = 0, 1, 2
 
+# DINO_FILTER_* (Pillow's resampling filters; bicubic is every recipe's default)
+RESAMPLE_FILTERS = {"bicubic": 0, "bilinear": 1, "box": 2, "hamming": 3, "lanczos": 4}
+_FILTER_SUPPORT2 = {0: 4, 1: 2, 2: 1, 3: 2, 4: 6}  # twice the support (csrc/common.hpp resample_support2)
+
+
+def resample_filter_code(f) -> int:
+    """``DINO_FILTER_*`` code of a filter given by name, by code or as None (bicubic)."""
+    if f is None:
+        return 0
+    if isinstance(f, str):
+        if f.lower() not in RESAMPLE_FILTERS:
+            raise ValueError(f"resample filter must be one of {sorted(RESAMPLE_FILTERS)}, not {f!r}")
+        return RESAMPLE_FILTERS[f.lower()]
+    if isinstance(f, bool) or int(f) != f or int(f) not in _FILTER_SUPPORT2:
+        raise ValueError(f"unknown resample filter code {f!r}")
+    return int(f)
+
+
+def resample_bound_scale(f) -> int:
+    """Factor on the probes' augment-workspace bound (stated for bicubic) that makes it safe
+    for filter ``f``: the support ratio rounded up (csrc/plan.hpp resample_bound_scale)."""
+    return (_FILTER_SUPPORT2[resample_filter_code(f)] + 3) // 4
+
 
 class DinoLimits(ctypes.Structure):
     _fields_ = [

@@ -42,7 +42,7 @@ import torch
 
 from . import fallback
 from .engine import IngestEngine, pack_jpegs, params_from_device
-from .params import OUT_BF16, OUT_FP8_E4M3, OUT_FP32, RECORD_BYTES, make_aug_config
+from .params import OUT_BF16, OUT_FP8_E4M3, OUT_FP32, RECORD_BYTES, make_aug_config, resample_filter_code
 
 _DTYPES = {"bf16": OUT_BF16, "fp32": OUT_FP32, "fp8": OUT_FP8_E4M3}
 
@@ -484,9 +484,11 @@ class MI355XAugPipeline:
                  view_names: list[str] | None = None, host_fallback: bool = True,
                  multiscan_route: str = "auto", host_workers: int | None = None,
                  multiscan_host_max: int | None = None, prefetch: int | None = None,
-                 start_host_pool: bool = False, side_ahead: int = 64):
+                 start_host_pool: bool = False, side_ahead: int = 64, resample_filter=None):
         self._source = source
         self._aug_cfg = aug_cfg
+        # Pillow filter of every view's resize (None: bicubic, or what a passed-in engine has)
+        self._resample_filter = None if resample_filter is None else resample_filter_code(resample_filter)
         self._batch_size = int(batch_size)
         self._resolution_src = resolution_src
         self._out = _out_code(out_dtype)
@@ -571,6 +573,9 @@ class MI355XAugPipeline:
                 eng = IngestEngine(device, max_batch=self._batch_size, max_views=aug_cfg.n_views,
                                    max_crop_size=max_crop, max_image_dim=max_image_dim,
                                    workspace_bytes=workspace_bytes, stream=stream)
+            # (the side contexts of progside.py only decode: the filter is not theirs to know)
+            if self._resample_filter is not None:
+                eng.set_resample_filter(self._resample_filter)
             self._slots.append(_Slot(eng))
         self._last: _Slot = self._slots[0]          # the last launched batch
         # output sets (shape key, tensors, consumer stream), batch n -> set n % (depth + 1)
@@ -1450,7 +1455,7 @@ class MI355XUserAugPipeline:
     undecodable image contributes zeros of shape (3, decode_size, decode_size)."""
 
     def __init__(self, source: Any, spec, batch_size: int, out_dtype="bf16", device: int = 0,
-                 max_image_dim: int = 0, workspace_bytes: int = 0, norm=None):
+                 max_image_dim: int = 0, workspace_bytes: int = 0, norm=None, resample_filter=None):
         self._source = source
         self._spec = spec
         self._batch_size = int(batch_size)
@@ -1459,6 +1464,8 @@ class MI355XUserAugPipeline:
         self._max_image_dim = int(max_image_dim)
         self._engine = IngestEngine(device, max_batch=self._batch_size, max_views=1, max_crop_size=8,
                                     max_image_dim=max_image_dim, workspace_bytes=workspace_bytes)
+        if resample_filter is not None:  # Pillow filter of the resize (None: bicubic)
+            self._engine.set_resample_filter(resample_filter)
         self.stats = {"batches": 0, "images": 0, "status": Counter(), "host_decoded": 0}
         self._pending_status: deque = deque()
         self._closed = False

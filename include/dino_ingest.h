@@ -45,7 +45,9 @@
  *    interpreter).  Round 6, still additive within ABI 4: dino_tar_index_fd (header-only
  *    tar index over a file descriptor), dino_ctx_set_prog_decoder (wave / lane decoder of
  *    progressive images per context), dino_copy_rgb_packed (a pool's images into one
- *    buffer in one launch).
+ *    buffer in one launch).  Still additive within ABI 4: dino_ctx_set_resample_filter
+ *    (Pillow's BILINEAR / BOX / HAMMING / LANCZOS per context; BICUBIC stays the default)
+ *    and dino_resample_coeffs_host.
  */
 #ifndef DINO_INGEST_H
 #define DINO_INGEST_H
@@ -321,6 +323,30 @@ int dino_masks_host(int32_t height, int32_t width, int32_t num_masking_patches, 
 #define DINO_PROG_LANES 1
 int dino_ctx_set_prog_decoder(dino_ctx* ctx, int32_t decoder);
 
+/* Resampling filter of this ctx's resizes, from the next call on: dino_augment,
+ * dino_run_batch* and dino_resize_batch.  The filters are Pillow's (libImaging/Resample.c
+ * as of 12.2), bit-exact with Image.resize(..., Image.<FILTER>): DINO_FILTER_BICUBIC is the
+ * default and what every reference CPU recipe uses (cpu.py:172-183); the reference's GPU peer
+ * resamples Eval views with EvalAugSpec.interpolation (pipeline.py:539).  An unknown code is
+ * DINO_EINVAL.  The probes (dino_probe*, dino_gather_probe, dino_augment_need, the feed)
+ * state the augment workspace for BICUBIC: for DINO_FILTER_LANCZOS reserve twice their
+ * aws_need (the support ratio rounded up; the other filters need no more than BICUBIC).
+ * A view that does not fit ends in DINO_IMG_NO_SPACE as ever. */
+#define DINO_FILTER_BICUBIC 0
+#define DINO_FILTER_BILINEAR 1
+#define DINO_FILTER_BOX 2
+#define DINO_FILTER_HAMMING 3
+#define DINO_FILTER_LANCZOS 4
+int dino_ctx_set_resample_filter(dino_ctx* ctx, int32_t filter);
+
+/* The coefficient code of the resample kernels run on the host (no GPU involved; tests and
+ * introspection): for in_size -> out_size with `filter`, *ksize = taps reserved per output;
+ * with taps != NULL also, for the outputs x0 .. x0 + n - 1, bounds[2 i] = first source index,
+ * bounds[2 i + 1] = tap count and taps[i * ksize + t] = the 22-bit fixed-point taps (zero
+ * padded).  taps NULL returns only *ksize. */
+int dino_resample_coeffs_host(int32_t filter, int32_t in_size, int32_t out_size, int32_t x0, int32_t n,
+                              int32_t* ksize, int32_t* bounds, int32_t* taps);
+
 /* Per-kernel HIP-event timing of this ctx's launches (bench / profiling).
  * Kernel ids: 0 parse, 1 plan, 2 destuff, 3 huff1, 4 idct, 5 color, 6 params,
  * 7 vplan, 8 rcoeffs, 9 hresize, 10 final(global views), 11 final(local views),
@@ -335,7 +361,10 @@ int dino_kernel_times(dino_ctx* ctx, double* total_ms, int64_t* counts, int32_t 
  * region (0 descriptor, 1 destuffed entropy bytes, 2 sparse DCT coefficient entries + block info,
  * 3 component planes, 4 RGB, 5 speculative Huffman lane records: 68 bytes per lane =
  * start state, range result, first-decode result, checkpoints, first block, 6 the scan-list
- * header of a kind-1 image: 832 bytes, int32 at byte 776 = 1 when the lane decoder took it)
+ * header of a kind-1 image: 832 bytes, int32 at byte 776 = 1 when the lane decoder took it,
+ * 7 the resample tables of the image's last dino_resize_batch: int32 hb[out_w][2] (first source
+ * index, tap count), ht[out_w][kh], then from the next multiple of 16 bytes vb[out_h][2],
+ * vt[out_h][kv], with kh / kv = dino_resample_coeffs_host's ksize, 0 for an axis not resampled)
  * into d_dst (<= max_bytes).  Synchronises the stream. */
 int dino_debug_region(dino_ctx* ctx, int32_t index, int32_t region, void* d_dst, int64_t max_bytes, void* stream);
 
