@@ -631,6 +631,14 @@ int dino_debug_region(dino_ctx* c, int32_t index, int32_t region, void* d_dst, i
       src = c->d_aws + vp.rcoef_off;
       n = vp.htmp_off - vp.rcoef_off;
       break;
+    case 8:  // region 1 with the 64-byte zero pad k_destuff_write puts after it
+      src = c->d_ws + d.ent_off;
+      n = d.kind == 0 ? std::min<int64_t>((int64_t)d.ent_len + 64, d.rst_off - d.ent_off) : 0;
+      break;
+    case 9:  // restart offsets (int32 per RSTn found: where the next interval starts in region 1)
+      src = c->d_ws + d.rst_off;
+      n = d.kind == 0 ? 4 * (int64_t)std::min(d.n_rst, d.n_rst_max + 1) : 0;
+      break;
     default: return fail(DINO_EINVAL, "dino_debug_region: region %s%lld", "", region);
   }
   if (d.status != 0 && region != 0) return fail(DINO_EINVAL, "dino_debug_region: image status %s%lld", "", d.status);

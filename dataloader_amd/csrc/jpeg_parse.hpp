@@ -60,6 +60,7 @@ DHD int parse_jpeg(const uint8_t* p, int64_t len, int max_dim, ImgDesc* d, bool 
   d->qt_seen_mask = 0;
   d->aug_status = 0;
   d->rst_bad = 0;
+  d->ent_len = d->n_rst = d->terminated = 0;  // (k_destuff_write fills them for a kind-0 image)
   d->total_blocks = 0;
   for (int i = 0; i < 8; ++i) d->huff_off[i] = -1;
   for (int t = 0; t < 4; ++t)

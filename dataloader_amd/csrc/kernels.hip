@@ -341,6 +341,7 @@ __device__ __forceinline__ void ds_clip(DsChunk& ch, int k0, int E) {
 // scan bytes [16c - lead, 16c - lead + 16)) and parts of kDsPartChunks chunks.
 constexpr int kDsTiles = 8;
 constexpr int kDsPartChunks = kDestuffThreads * kDsTiles;  // 32 KiB of scan per work item
+static_assert(kDsPartChunks * 16 == kDsPartBytes, "ds_parts / ds_part_role (plan.hpp) count the same parts");
 struct DsGeom {
   const uint8_t* r;
   int n, lead, nchunks;
@@ -481,8 +482,8 @@ __global__ void __launch_bounds__(kDestuffThreads) k_destuff_write(const uint8_t
     }
     __syncthreads();
     const int E = s_E;
-    const int part_k0 = part * kDsPartChunks * 16 - g.lead;
-    if (part_k0 < E || (part == 0)) {
+    const DsRole role = ds_part_role(part, g.lead, g.n, E, d->ds_items);
+    if (role.writes || role.finalises) {
       uint8_t* out = ws + d->ent_off;
       int32_t* rst = (int32_t*)(ws + d->rst_off);
       const int nrst_cap = d->n_rst_max + 1;
@@ -534,10 +535,8 @@ __global__ void __launch_bounds__(kDestuffThreads) k_destuff_write(const uint8_t
         o_run += tot & 0xFFFFu;
         rc_run += tot >> 16;
       }
-      // the part that ends the stream: holds E, or is the image's last part
-      const int part_k1 = part_k0 + kDsPartChunks * 16;
-      const bool last = (E < g.n) ? (E >= part_k0 && E < part_k1) : (part == d->ds_items - 1);
-      if (last) {
+      // the part that ends the stream: holds E, or is the image's last part (ds_part_role)
+      if (role.finalises) {
         const int total = (int)o_run;
         for (int k = total + t; k < total + 64 && k < g.n + 64; k += kDestuffThreads) out[k] = 0;
         if (t == 0) {

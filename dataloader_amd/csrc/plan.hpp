@@ -64,6 +64,23 @@ DHD int ds_parts(const ImgDesc& d) {
   return n > 1 ? n : 1;
 }
 
+// What part `part` of an image's ds_items parts does in k_destuff_write.  The scan has n
+// bytes, the first of them `lead` bytes into part 0 (part p covers scan indices
+// [p kDsPartBytes - lead, (p + 1) kDsPartBytes - lead)); E is the scan index of the first
+// terminating marker, n when there is none.  A part writes the kept bytes of its range
+// below E.  Exactly one part completes the descriptor (ent_len, n_rst, terminated, the
+// TRUNCATED status, the 64-byte zero pad): the part whose range holds E, or the image's
+// last part when nothing terminates the scan; it does so even when it writes no byte (E
+// on its first byte; a last part past the end of a scan cut short).  ds_parts sizes from
+// scan_len + 16 >= E + lead + 1, so the part that holds E exists.
+struct DsRole {
+  bool writes, finalises;
+};
+DHD DsRole ds_part_role(int part, int lead, int n, int E, int ds_items) {
+  const int k0 = part * kDsPartBytes - lead, k1 = k0 + kDsPartBytes;
+  return {k0 < E, E < n ? (E >= k0 && E < k1) : part == ds_items - 1};
+}
+
 DHD ChunkSizes image_chunk_bytes(const ImgDesc& d) {
   ChunkSizes z{};
   if (d.status != DINO_IMG_OK) return z;

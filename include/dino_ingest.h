@@ -364,7 +364,9 @@ int dino_kernel_times(dino_ctx* ctx, double* total_ms, int64_t* counts, int32_t 
  * header of a kind-1 image: 832 bytes, int32 at byte 776 = 1 when the lane decoder took it,
  * 7 the resample tables of the image's last dino_resize_batch: int32 hb[out_w][2] (first source
  * index, tap count), ht[out_w][kh], then from the next multiple of 16 bytes vb[out_h][2],
- * vt[out_h][kv], with kh / kv = dino_resample_coeffs_host's ksize, 0 for an axis not resampled)
+ * vt[out_h][kv], with kh / kv = dino_resample_coeffs_host's ksize, 0 for an axis not resampled,
+ * 8 region 1 followed by the 64 zero bytes the destuffing pass puts after it, 9 the restart
+ * offsets of a baseline image: one int32 per RSTn found, where the next interval starts in region 1)
  * into d_dst (<= max_bytes).  Synchronises the stream. */
 int dino_debug_region(dino_ctx* ctx, int32_t index, int32_t region, void* d_dst, int64_t max_bytes, void* stream);
 

@@ -115,6 +115,49 @@ int emu_decode_stages(const uint8_t* p, int64_t len, int mode, int lanes, uint8_
   return r;
 }
 
+// ---- destuffing ---------------------------------------------------------------
+// model_destuff over a scan of n bytes: info = {len, n_rst, terminated, rst_bad}; the bytes
+// with their zero pad into `bytes` (up to cap; returns how many there are) and the restart
+// offsets into `rst` (up to rst_cap).
+int64_t emu_destuff(const uint8_t* scan, int n, uint8_t* bytes, int64_t cap, int32_t* rst, int32_t rst_cap,
+                    int32_t* info) {
+  const Destuffed d = model_destuff(scan, n);
+  info[0] = d.len;
+  info[1] = (int32_t)d.rst.size();
+  info[2] = d.terminated;
+  info[3] = d.rst_bad;
+  memcpy(bytes, d.bytes.data(), (size_t)std::min<int64_t>(cap, (int64_t)d.bytes.size()));
+  memcpy(rst, d.rst.data(), 4 * (size_t)std::min<int64_t>(rst_cap, (int64_t)d.rst.size()));
+  return (int64_t)d.bytes.size();
+}
+
+// ds_parts of a baseline scan of scan_len bytes, and ds_part_role (plan.hpp)
+int emu_ds_parts(int scan_len) {
+  ImgDesc d{};
+  d.status = DINO_IMG_OK;
+  d.kind = 0;
+  d.scan_len = scan_len;
+  return ds_parts(d);
+}
+
+// over every part of one image: out[2 p] = writes, out[2 p + 1] = finalises
+void emu_ds_part_roles(int lead, int n, int E, int ds_items, uint8_t* out) {
+  for (int p = 0; p < ds_items; ++p) {
+    const DsRole r = ds_part_role(p, lead, n, E, ds_items);
+    out[2 * p] = r.writes;
+    out[2 * p + 1] = r.finalises;
+  }
+}
+
+// offsetof of the descriptor fields k_destuff_write fills (dino_debug_region 0):
+// out = {status, scan_off, scan_len, ent_len, n_rst, terminated, rst_bad, sizeof(ImgDesc)}.
+void emu_desc_layout(int32_t* out) {
+  const size_t v[8] = {offsetof(ImgDesc, status),  offsetof(ImgDesc, scan_off),   offsetof(ImgDesc, scan_len),
+                       offsetof(ImgDesc, ent_len), offsetof(ImgDesc, n_rst),      offsetof(ImgDesc, terminated),
+                       offsetof(ImgDesc, rst_bad), sizeof(ImgDesc)};
+  for (int i = 0; i < 8; ++i) out[i] = (int32_t)v[i];
+}
+
 // Per-scan symbol counts of a multi-scan image (analysis aid): out[i] = symbols of scan
 // i, levels[i] = its dependency level; returns the number of scans (< 0: status).
 int emu_prog_scan_stats(const uint8_t* p, int64_t len, int64_t* out, int32_t* levels, int32_t cap) {
