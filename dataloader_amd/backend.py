@@ -121,7 +121,8 @@ class MI355XBackend:
 
     def __init__(self, max_image_dim: int = 0, workspace_bytes: int = 0, max_in_flight: int = 3,
                  hbm_fraction: float = 0.15, host_workers: int | None = None, multiscan_route: str = "side",
-                 side_ahead: int | None = None, resample_filter: str | None = None) -> None:
+                 side_ahead: int | None = None, resample_filter: str | None = None,
+                 four_component: str = "host") -> None:
         # Pillow filter of every resize: None = bicubic everywhere (CPUBackend parity, which
         # ignores EvalAugSpec.interpolation too); a filter's name applies to every recipe;
         # "spec" honours EvalAugSpec.interpolation as the reference's GPU peer does
@@ -131,6 +132,13 @@ class MI355XBackend:
                 raise ValueError(f"resample_filter must be a filter's name, 'spec' or None, not {resample_filter!r}")
             resample_filter_code(resample_filter)  # ValueError on an unknown name
         self._resample_filter = resample_filter
+        # four-component (Adobe CMYK / YCCK) JPEGs: "host" (default) hands them to Pillow worker
+        # processes; "device" decodes them in the HIP kernels, bit-exact with Pillow's
+        # convert("RGB"), on the multi-scan route (each costs a progressive file's latency; the
+        # side route decodes them ahead of their batch).  The UserAugSpec pipeline hands them over
+        if four_component not in ("host", "device"):
+            raise ValueError(f"four_component must be 'host' or 'device', not {four_component!r}")
+        self._four_component = four_component
         self._max_image_dim = max_image_dim
         self._workspace_bytes = workspace_bytes
         self._max_in_flight = max(1, int(max_in_flight))
@@ -283,6 +291,7 @@ class MI355XBackend:
             multiscan_route=self._multiscan_route,
             side_ahead=self.side_look_ahead(pipeline_cfg, source, depth),
             resample_filter=self.spec_filter(aug_spec),
+            four_component=self._four_component,
         )
 
     def build_pipeline_iterator(self, pipeline: Any, aug_spec: Any, output_map: list[str],

@@ -63,6 +63,7 @@ struct dino_ctx {
   hipStream_t ws_stream = nullptr;  // stream of the last dino_reserve (the workspaces' release order)
   LaunchGeom geom{};
   int32_t filter = kBicubic;  // dino_ctx_set_resample_filter: read at each augment / resize launch
+  int32_t four_component = 0; // dino_ctx_set_four_component: read at each decode launch
   KernelTimer* timer = nullptr;
   KernelTimer* tm() { return timer && timer->enabled ? timer : nullptr; }
 };
@@ -147,7 +148,7 @@ int dino_decode_spans(dino_ctx* c, const uint8_t* d_bytes, const int64_t* d_offs
     return fail(DINO_EINVAL, "dino_decode: batch %s%lld exceeds ctx max_batch", "", batch);
   hipStream_t s = (hipStream_t)stream;
   DecodeArgs a{d_bytes, d_offsets, d_lengths, d_raw_mask, batch, c->lim.max_image_dim, c->d_desc, c->d_ws,
-               c->ws_size, c->geom, c->d_pctl};
+               c->ws_size, c->geom, c->d_pctl, c->four_component};
   hipError_t e = launch_decode(a, s, c->tm());
   if (e != hipSuccess) return hip_fail(e, "dino_decode");
   if (d_info && (e = launch_info(c->d_desc, batch, d_info, s)) != hipSuccess) return hip_fail(e, "dino_decode(info)");
@@ -321,7 +322,8 @@ int dino_augment_need(const int32_t* info, int32_t batch, const dino_aug_config*
   if (!info || batch < 0 || !cfg || !aws_need) return fail(DINO_EINVAL, "dino_augment_need: bad arguments%s%lld");
   int64_t aws = 0;
   for (int32_t i = 0; i < batch; ++i) {
-    if (info[4 * i] != DINO_IMG_OK) continue;
+    // (kind 3: a four-component image, which a context with the option on decodes)
+    if (info[4 * i] != DINO_IMG_OK && !(info[4 * i] == DINO_IMG_UNSUPPORTED && info[4 * i + 3] == 3)) continue;
     for (int v = 0; v < cfg->n_global + cfg->n_local; ++v)
       aws += view_scratch_bound(v < cfg->n_global ? cfg->global_size : cfg->local_size, info[4 * i + 1],
                                 info[4 * i + 2]);
@@ -545,6 +547,12 @@ int dino_ctx_set_prog_decoder(dino_ctx* c, int32_t decoder) {
   if (decoder != DINO_PROG_WAVE && decoder != DINO_PROG_LANES)
     return fail(DINO_EINVAL, "dino_ctx_set_prog_decoder: unknown decoder%s %lld", "", (long long)decoder);
   c->geom.prog_lane = decoder == DINO_PROG_LANES;  // read at each launch (launch_decode)
+  return DINO_OK;
+}
+
+int dino_ctx_set_four_component(dino_ctx* c, int32_t on) {
+  if (!c) return fail(DINO_EINVAL, "dino_ctx_set_four_component: null ctx%s%lld");
+  c->four_component = on != 0;  // read at each launch (launch_decode)
   return DINO_OK;
 }
 

@@ -79,4 +79,33 @@ DHD void ycc_to_rgb(int y, int cb, int cr, uint8_t* rgb) {
   rgb[2] = clamp255(y + b_add);
 }
 
+// libImaging ImagingUtils.h MULDIV255: a * b / 255, rounded.
+DHD int muldiv255(int a, int b) {
+  const int t = a * b + 128;
+  return ((t >> 8) + t) >> 8;
+}
+
+// One pixel of a four-component frame: the four upsampled samples as libjpeg hands them
+// to Pillow (out_color_space JCS_CMYK) -> the RGB of Image.open(..).convert("RGB").
+//  1. jdcolor.c ycck_cmyk_convert (YCCK frames only): R, G, B from ycc_rgb_convert's
+//     tables, C / M / Y = 255 - R / G / B (MAXJSAMPLE - ..., range-limited), K copied;
+//  2. Pillow reads every 4-layer JPEG with raw mode "CMYK;I" (JpegImagePlugin.py
+//     _open / load: "assume adobe conventions"; Unpack.c unpackCMYKI): all four bytes
+//     are inverted, 255 - x;
+//  3. Convert.c cmyk2rgb: nk = 255 - K, r = CLIP8(nk - MULDIV255(C, nk)), g and b alike.
+DHD void four_to_rgb(int s0, int s1, int s2, int s3, bool ycck, uint8_t* rgb) {
+  if (ycck) {
+    uint8_t t[3];
+    ycc_to_rgb(s0, s1, s2, t);
+    s0 = 255 - t[0];
+    s1 = 255 - t[1];
+    s2 = 255 - t[2];
+  }
+  const int c = 255 - s0, m = 255 - s1, y = 255 - s2, k = 255 - s3;
+  const int nk = 255 - k;
+  rgb[0] = clamp255(nk - muldiv255(c, nk));
+  rgb[1] = clamp255(nk - muldiv255(m, nk));
+  rgb[2] = clamp255(nk - muldiv255(y, nk));
+}
+
 }  // namespace dino

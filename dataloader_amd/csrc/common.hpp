@@ -16,11 +16,12 @@
 
 namespace dino {
 
-constexpr int kMaxComp = 3;
+constexpr int kMaxComp = 3;             // components of an image the speculative Huffman and lane decoders take
+constexpr int kMaxFrameComp = 4;        // components of a frame (CMYK / YCCK: coefficient-buffer path only)
 constexpr int kMaxBlocksPerMcu = 10;   // libjpeg D_MAX_BLOCKS_IN_MCU
 constexpr int kLookBits = 11;          // Huffman lookahead table bits
 
-enum ColorSpace : int32_t { kGray = 0, kYCbCr = 1, kRGB = 2 };
+enum ColorSpace : int32_t { kGray = 0, kYCbCr = 1, kRGB = 2, kCMYK = 3, kYCCK = 4 };
 
 struct CompDesc {
   int32_t id, h, v, tq, td, ta;
@@ -46,7 +47,6 @@ struct ImgDesc {
   uint8_t mcu_by[kMaxBlocksPerMcu];
   uint8_t pad0[2];
   uint16_t qt[4][64];      // quant tables, natural order
-  CompDesc comp[kMaxComp];
   int32_t total_blocks;    // MCUs * blocks_per_mcu
   // filled by k_plan (byte offsets into the ctx workspace)
   int64_t base;            // start of this image's chunk
@@ -81,7 +81,13 @@ struct ImgDesc {
   int32_t n_scans;         // kind 1: scans (k_prog)
   int32_t qt_seen_mask;    // DQT slots defined before the first SOS
   int32_t aug_status;      // DINO_IMG_NO_SPACE when k_vplan could not place one of its views
+  // Last, so that everything up to comp[kMaxComp] is the descriptor of a one- or three-component
+  // image: the speculative Huffman kernels stage only that much in LDS (kSpecDescBytes); the
+  // fourth component is read by the frame-level stages (k_pwalk, k_pscan, k_idct, k_color) only
+  CompDesc comp[kMaxFrameComp];
 };
+constexpr size_t kSpecDescBytes = offsetof(ImgDesc, comp) + kMaxComp * sizeof(CompDesc);
+static_assert(kSpecDescBytes % 8 == 0 && kSpecDescBytes + sizeof(CompDesc) == sizeof(ImgDesc), "ImgDesc layout");
 
 // Resampling filter of a context (include/dino_ingest.h DINO_FILTER_*, Pillow's names).
 // 0 is BICUBIC, so that every zero-initialised structure means the one filter there was.

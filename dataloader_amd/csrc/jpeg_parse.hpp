@@ -48,7 +48,10 @@ DHD int check_dims(ImgDesc* d, int max_dim) {
 // dino_decode / dino_probe).  The container's magic is never trusted in user data: an
 // unmarked file that starts with it is parsed as what it is (not a JPEG -> corrupt, as
 // Pillow would raise).
-DHD int parse_jpeg(const uint8_t* p, int64_t len, int max_dim, ImgDesc* d, bool allow_raw = false) {
+// four_component: decode four-component frames (Adobe CMYK / YCCK) on the coefficient-buffer
+// path (dino_ctx_set_four_component); off, they are DINO_IMG_UNSUPPORTED at the SOF marker.
+DHD int parse_jpeg(const uint8_t* p, int64_t len, int max_dim, ImgDesc* d, bool allow_raw = false,
+                   bool four_component = false) {
   d->status = DINO_IMG_CORRUPT;
   d->width = d->height = d->ncomp = 0;
   d->restart_interval = 0;
@@ -116,7 +119,8 @@ DHD int parse_jpeg(const uint8_t* p, int64_t len, int max_dim, ImgDesc* d, bool 
         // 1, 3, 4 (JpegImagePlugin.SOF): the reference zero-fills those
         if (prec != 8) return (d->status = DINO_IMG_CORRUPT);
         if (nf != 1 && nf != 3 && nf != 4) return (d->status = DINO_IMG_CORRUPT);
-        if (nf == 4) return (d->status = DINO_IMG_UNSUPPORTED);  // CMYK / YCCK
+        if (nf == 4 && !four_component) return (d->status = DINO_IMG_UNSUPPORTED);  // CMYK / YCCK
+        if (nf == 4) d->ncomp = 4;  // (the probes tell a four-component file by it whatever fails later)
         if (d->height == 0) return (d->status = DINO_IMG_UNSUPPORTED);  // DNL
         if (d->width == 0) return (d->status = DINO_IMG_CORRUPT);
         d->ncomp = nf;
@@ -198,7 +202,9 @@ DHD int parse_jpeg(const uint8_t* p, int64_t len, int max_dim, ImgDesc* d, bool 
         // scans, another component order) on the coefficient-buffer path (k_prog),
         // whose marker walk re-reads this SOS.
         d->first_sos = (int32_t)(pos - 2);  // (a baseline image may still move to k_prog, k_destuff_write)
-        bool one_scan = !d->progressive && ns == d->ncomp;
+        // (a four-component frame always takes the coefficient-buffer path: the speculative
+        // Huffman kernels are sized for kMaxComp components)
+        bool one_scan = !d->progressive && ns == d->ncomp && d->ncomp <= kMaxComp;
         for (int k = 0; k < ns && one_scan; ++k) {
           int cs = s[1 + 2 * k];
           int ci = -1;
@@ -245,6 +251,10 @@ have_scan:
   // colour space (jdapimin.c default_decompress_parms)
   if (d->ncomp == 1) {
     d->color = kGray;
+  } else if (d->ncomp == 4) {
+    // case 4: an Adobe marker with transform 0 is CMYK, 2 is YCCK, any other value YCCK
+    // too (WARNMS1 JWRN_ADOBE_XFORM); without an Adobe marker CMYK.  JFIF plays no part.
+    d->color = saw_adobe && adobe_transform != 0 ? kYCCK : kCMYK;
   } else if (saw_jfif) {
     d->color = kYCbCr;
   } else if (saw_adobe) {

@@ -8,6 +8,8 @@
 //                                   work items of 256 lanes (see the Huffman section)
 //   k_idct      lanes over blocks   islow IDCT (int32 fast path, int64 exact fallback)
 //   k_color     lanes over pixels   fancy upsampling + YCbCr->RGB
+//   k_idct4 / k_color4              the same for four-component frames (CMYK / YCCK), launched
+//                                   only by a context with dino_ctx_set_four_component on
 // Augment half (per view):
 //   k_params    1 lane / view       Philox draw of the view record (optional)
 //   k_vplan     1 workgroup         per-view scratch offsets
@@ -70,7 +72,7 @@ constexpr int kParsePrefix = 4096;
 __global__ void __launch_bounds__(64) k_parse(const uint8_t* __restrict__ bytes, const int64_t* __restrict__ offsets,
                                               const int64_t* __restrict__ lengths,
                                               const uint8_t* __restrict__ raw_mask, int B, int max_dim,
-                                              ImgDesc* __restrict__ desc) {
+                                              int four_component, ImgDesc* __restrict__ desc) {
   __shared__ __attribute__((aligned(16))) uint8_t s_raw[kParsePrefix + 16];
   const int i = blockIdx.x;
   const int64_t off = offsets[i], len = lengths ? lengths[i] : offsets[i + 1] - off;
@@ -103,13 +105,16 @@ __global__ void __launch_bounds__(64) k_parse(const uint8_t* __restrict__ bytes,
     d.aug_status = 0;
   } else {
     const bool raw = raw_mask != nullptr && raw_mask[i] != 0;
-    parse_jpeg(s_head, n, max_dim, &d, raw);
+    parse_jpeg(s_head, n, max_dim, &d, raw, four_component != 0);
     if (n < len) {
       if (d.status == DINO_IMG_OK && !raw) d.scan_len = (int32_t)(len - d.scan_off);
-      else parse_jpeg(src, len, max_dim, &d, raw);
+      else parse_jpeg(src, len, max_dim, &d, raw, four_component != 0);
     }
   }
-  desc[i] = d;
+  // (the descriptor of a one- or three-component image ends before comp[kMaxComp]: the same
+  // bytes as before there were four-component frames; the copy is lane 0's, serial)
+  __builtin_memcpy(&desc[i], &d, kSpecDescBytes);
+  if (d.ncomp > kMaxComp) desc[i].comp[kMaxComp] = d.comp[kMaxComp];
 }
 
 // ---------------------------------------------------------------------------
@@ -860,7 +865,7 @@ __device__ bool huff_load_item(LdsT& L, const ImgDesc* desc, int B, const uint8_
   if (threadIdx.x == 0) {
     L.img = huff_item_image(desc, B, item);
     if (L.img >= 0) {
-      L.sd = desc[L.img];
+      __builtin_memcpy(&L.sd, &desc[L.img], kSpecDescBytes);  // (kind 0: at most kMaxComp components)
       if (skip_single && huff_single_segment(L.sd)) L.img = -2;
     }
   }
@@ -2355,14 +2360,18 @@ __device__ __forceinline__ uint64_t idct_group_pass2(int32_t* sb, int l) {
   return o.u;
 }
 
-__global__ void __launch_bounds__(256) k_idct(const ImgDesc* __restrict__ desc, uint8_t* __restrict__ ws) {
+// kComps: the frame components the instance can address (3: k_idct, every image of up to three
+// components, the code it always was; 4: k_idct4, launched only by a context with
+// dino_ctx_set_four_component on, for the four-component images k_idct leaves alone).
+template <int kComps>
+__device__ __forceinline__ void idct_image(const ImgDesc* __restrict__ desc, uint8_t* __restrict__ ws) {
   const BlkIdx bk = xcd_blk();
   // rows of 9 words, blocks 72 words apart: both the column (pass 1) and the row
   // (pass 2) accesses of a wave's 8 groups x 8 lanes hit 64 distinct banks
   __shared__ int32_t s_blk[kIdctBlocksPerWg][72];
   __shared__ uint8_t s_nat[80];
   const ImgDesc& d = desc[bk.y];
-  if (d.status != DINO_IMG_OK || d.kind == 2) return;
+  if (d.status != DINO_IMG_OK || d.kind == 2 || (d.ncomp > kMaxComp) != (kComps > kMaxComp)) return;
   // kind 1 (progressive / multi-scan): dense int16 coefficients in natural order,
   // component planes of bw x bh blocks (k_prog); kind 0: sparse entries + block records
   const bool dense = d.kind == 1;
@@ -2371,17 +2380,19 @@ __global__ void __launch_bounds__(256) k_idct(const ImgDesc* __restrict__ desc, 
   const int64_t nb0 = (int64_t)d.comp[0].bw * d.comp[0].bh;
   const int64_t nb1 = ncomp > 1 ? (int64_t)d.comp[1].bw * d.comp[1].bh : 0;
   const int64_t nb2 = ncomp > 2 ? (int64_t)d.comp[2].bw * d.comp[2].bh : 0;
-  const int64_t tot = nb0 + nb1 + nb2;
+  const int64_t nb3 = kComps > 3 && ncomp > 3 ? (int64_t)d.comp[3].bw * d.comp[3].bh : 0;  // (kind 1 only)
+  const int64_t tot = nb0 + nb1 + nb2 + nb3;
   const uint32_t* ent = (const uint32_t*)(ws + d.coef_off);
   const uint2* binfo = (const uint2*)(ws + d.binfo_off);
   uint8_t* planes = ws + d.plane_off;
   // first position of each component inside the MCU (interleaved scans)
-  int moff[kMaxComp] = {0, 0, 0};
+  int moff[kMaxFrameComp] = {0, 0, 0, 0};
   for (int i = d.blocks_per_mcu - 1; i >= 0; --i) {
     const int c = d.mcu_comp[i];
     if (c == 0) moff[0] = i;
     else if (c == 1) moff[1] = i;
-    else moff[2] = i;
+    else if (kComps <= 3 || c == 2) moff[2] = i;
+    else moff[3] = i;
   }
   const int grp = threadIdx.x >> 3, l = threadIdx.x & 7;
   int32_t* sb = s_blk[grp];
@@ -2392,15 +2403,15 @@ __global__ void __launch_bounds__(256) k_idct(const ImgDesc* __restrict__ desc, 
   };
   auto locate = [&](int g) {
     Blk r;
-    r.c = g < nb0 ? 0 : (g < nb0 + nb1 ? 1 : 2);
-    const int k = g - (r.c == 0 ? 0 : (r.c == 1 ? (int)nb0 : (int)(nb0 + nb1)));
+    r.c = g < nb0 ? 0 : (g < nb0 + nb1 ? 1 : (kComps <= 3 || g < nb0 + nb1 + nb2 ? 2 : 3));
+    const int k = g - (r.c == 0 ? 0 : (r.c == 1 ? (int)nb0 : (r.c == 2 ? (int)(nb0 + nb1) : (int)(nb0 + nb1 + nb2))));
     const CompDesc& cd = d.comp[r.c];
     r.by = k / cd.bw;
     r.bx = k - r.by * cd.bw;
     if (ncomp == 1) {
       r.b = r.bx < d.mcus_x ? r.by * d.mcus_x + r.bx : -1;
     } else {
-      const int mo = r.c == 0 ? moff[0] : (r.c == 1 ? moff[1] : moff[2]);
+      const int mo = r.c == 0 ? moff[0] : (r.c == 1 ? moff[1] : (kComps <= 3 || r.c == 2 ? moff[2] : moff[3]));
       const int my = r.by / cd.v, mx = r.bx / cd.h;
       r.b = (my * d.mcus_x + mx) * d.blocks_per_mcu + mo + (r.by - my * cd.v) * cd.h + (r.bx - mx * cd.h);
     }
@@ -2450,6 +2461,13 @@ __global__ void __launch_bounds__(256) k_idct(const ImgDesc* __restrict__ desc, 
     if (gn < T) first_entries();
     wave_lds_sync();
   }
+}
+
+__global__ void __launch_bounds__(256) k_idct(const ImgDesc* __restrict__ desc, uint8_t* __restrict__ ws) {
+  idct_image<kMaxComp>(desc, ws);
+}
+__global__ void __launch_bounds__(256) k_idct4(const ImgDesc* __restrict__ desc, uint8_t* __restrict__ ws) {
+  idct_image<kMaxFrameComp>(desc, ws);
 }
 
 // ---------------------------------------------------------------------------
@@ -2505,6 +2523,70 @@ constexpr int kColorWgs = DINO_COLOR_WGS;  // workgroups per image
 #endif
 constexpr int kColorBatch = DINO_COLOR_BATCH;  // quads whose loads a lane issues together (measured: 4 and 8 slower)
 
+// k_color4: four-component frames (CMYK / YCCK; color.hpp four_to_rgb), four consecutive pixels
+// per lane and one band of rows per workgroup as k_color.  A kernel of its own, launched only by
+// a context with dino_ctx_set_four_component on (no other context has such an image to
+// convert): inside k_color its registers added to the three-component paths' (17 SGPRs of
+// k_color spilled, some in the 4:2:0 loop).  When no component is subsampled (what
+// Pillow and Photoshop write) a quad inside one row reads one word per plane (two when x is
+// not a multiple of 4: both lie inside the row, whose pitch is a multiple of 8); a quad that
+// wraps a row and every other sampling go per pixel through upsample_at's clamps.
+__global__ void __launch_bounds__(256) k_color4(const ImgDesc* __restrict__ desc, uint8_t* __restrict__ ws) {
+  const BlkIdx bk = xcd_blk();
+  const ImgDesc& d = desc[bk.y];
+  if (d.status != DINO_IMG_OK || d.ncomp != 4) return;
+  const PlaneView p0 = make_plane_view(d, ws, 0), p1 = make_plane_view(d, ws, 1);
+  const PlaneView p2 = make_plane_view(d, ws, 2), p3 = make_plane_view(d, ws, 3);
+  const bool ycck = d.color == kYCCK;
+  const bool full = p0.method == kUpFull && p1.method == kUpFull && p2.method == kUpFull && p3.method == kUpFull;
+  uint32_t* rgb = (uint32_t*)(ws + d.rgb_off);
+  const int W = d.width;
+  const int64_t npx = (int64_t)W * d.height;  // < 2^31 (check_dims)
+  const int64_t nq = (npx + 3) >> 2;
+  const int64_t band = ((nq + gridDim.x - 1) / gridDim.x + blockDim.x - 1) / blockDim.x * blockDim.x;
+  const int64_t qend = min(nq, (int64_t)(bk.x + 1) * band);
+  for (int64_t q = (int64_t)bk.x * band + threadIdx.x; q < qend; q += blockDim.x) {
+    const int64_t i0 = q * 4;
+    int y = (int)((uint32_t)i0 / (uint32_t)W), x = (int)((uint32_t)i0 - (uint32_t)y * (uint32_t)W);
+    union {
+      uint8_t b[12];
+      uint32_t w[3];
+    } o;
+    if (full && x + 3 < W) {
+      const uint32_t sh = (uint32_t)(x & 3);
+      uint32_t s[4];
+      const PlaneView* pv[4] = {&p0, &p1, &p2, &p3};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const uint32_t* r = (const uint32_t*)(pv[c]->p + (int64_t)y * pv[c]->pitch + (x & ~3));
+        const uint32_t lo = r[0], hi = sh ? r[1] : 0u;
+        s[c] = __builtin_amdgcn_alignbyte(hi, lo, sh);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        four_to_rgb((int)((s[0] >> (8 * j)) & 255u), (int)((s[1] >> (8 * j)) & 255u), (int)((s[2] >> (8 * j)) & 255u),
+                    (int)((s[3] >> (8 * j)) & 255u), ycck, o.b + 3 * j);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (i0 + j < npx) {
+          four_to_rgb(upsample_at(p0, x, y), upsample_at(p1, x, y), upsample_at(p2, x, y), upsample_at(p3, x, y), ycck,
+                      o.b + 3 * j);
+        } else {
+          o.b[3 * j] = o.b[3 * j + 1] = o.b[3 * j + 2] = 0;
+        }
+        if (++x == W) {
+          x = 0;
+          ++y;
+        }
+      }
+    }
+    rgb[3 * q] = o.w[0];
+    rgb[3 * q + 1] = o.w[1];
+    rgb[3 * q + 2] = o.w[2];
+  }
+}
+
 // Four consecutive pixels per lane (12 output bytes = three aligned dword stores;
 // the RGB area is padded by 16 bytes, so the last partial quad may store whole words).
 // 4:2:0 interior quads (the common case) take a vectorised path: one word of Y and
@@ -2528,6 +2610,7 @@ __global__ void __launch_bounds__(256) k_color(const uint8_t* __restrict__ bytes
     }
     return;
   }
+  if (d.ncomp == 4) return;  // CMYK / YCCK: k_color4
   const int nc = d.ncomp;
   const PlaneView p0 = make_plane_view(d, ws, 0);
   const PlaneView p1 = nc > 1 ? make_plane_view(d, ws, 1) : p0;
@@ -4135,7 +4218,8 @@ hipError_t init_launch_geom(int device, LaunchGeom* g) {
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
   const int B = a.batch;
   if (B <= 0) return hipSuccess;
-  TIMED(tm, kKParse, s, (k_parse<<<B, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.max_dim, a.desc)));
+  TIMED(tm, kKParse, s, (k_parse<<<B, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.max_dim, a.four_component,
+                                                  a.desc)));
   TIMED(tm, kKPlan, s, (k_plan<<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
   const int grid_ds = a.geom.grid_ds, grid1 = a.geom.grid1, grid3 = a.geom.grid3;
   TIMED(tm, kKDestuff, s, (k_destuff_count<<<grid_ds, kDestuffThreads, 0, s>>>(a.bytes, a.offsets, B, a.desc, a.ws)));
@@ -4156,7 +4240,9 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
   TIMED(tm, kKHuff3, s, (k_huff3<<<grid3, kHuffThreads, kHuff3LdsBytes, s>>>(a.desc, B, a.ws)));
   TIMED(tm, kKDcscan, s, (k_dcscan<<<B, kDcScanThreads, 0, s>>>(a.desc, a.ws)));
   TIMED(tm, kKIdct, s, (k_idct<<<dim3(kIdctWgs, B), 256, 0, s>>>(a.desc, a.ws)));
+  if (a.four_component) TIMED(tm, kKIdct, s, (k_idct4<<<dim3(kIdctWgs, B), 256, 0, s>>>(a.desc, a.ws)));
   TIMED(tm, kKColor, s, (k_color<<<dim3(kColorWgs, B), 256, 0, s>>>(a.bytes, a.offsets, a.desc, a.ws)));
+  if (a.four_component) TIMED(tm, kKColor, s, (k_color4<<<dim3(kColorWgs, B), 256, 0, s>>>(a.desc, a.ws)));
   return hipGetLastError();
 }
 

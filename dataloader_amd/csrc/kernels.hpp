@@ -89,6 +89,7 @@ struct DecodeArgs {
   int64_t ws_size;
   LaunchGeom geom;
   PCtl* pctl;
+  int32_t four_component;   // 1: four-component frames decode (dino_ctx_set_four_component), 0: DINO_IMG_UNSUPPORTED
 };
 
 // Output pointers travel as a kernel argument (no host->device copy whose source

@@ -227,8 +227,8 @@ DHD void lane_scan_decode(R& r, const T& t, D d, const ScanRec& sr, Out& o) {
   int32_t eobrun = 0;
   if (ss > 0) {  // AC scans: one component, one block per MCU (start_pass_phuff_decoder)
     const int ci = (int)g.comp;
-    const int64_t plane = sel3(g.plane, ci);
-    const int32_t bw = sel3(g.bw, ci), mcx = g.mcus_x, mcy = g.mcus_y;
+    const int64_t plane = selc(g.plane, ci);
+    const int32_t bw = selc(g.bw, ci), mcx = g.mcus_x, mcy = g.mcus_y;
     const uint64_t band = (uint64_t)low_bits(se + 1) & ~(uint64_t)low_bits(ss);
     const bool refine = sr.ah > 0;
     const int32_t nblk = mcx * mcy;

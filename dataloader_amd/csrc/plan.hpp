@@ -86,9 +86,9 @@ DHD ChunkSizes image_chunk_bytes(const ImgDesc& d) {
   if (d.status != DINO_IMG_OK) return z;
   z.rgb = align16((int64_t)d.width * d.height * 3 + 16);
   if (d.kind == 2) return chunk_finish(z);
-  int64_t p = 0;
-  for (int c = 0; c < d.ncomp; ++c) p += (int64_t)d.comp[c].bw * d.comp[c].bh * 64;
-  z.plane = align16(p);
+  // the planes hold a byte per coefficient of the dense int16 layout coef_bytes counts
+  // (jpeg_parse.hpp: 64 and 128 bytes a block of every component's bw x bh grid)
+  z.plane = align16(d.coef_bytes / 2);
   if (d.kind == 1) {
     z.ent = align16((int64_t)d.scan_len + 64);  // each scan's destuffed bytes (k_pscan)
     z.coef = align16(d.coef_bytes);

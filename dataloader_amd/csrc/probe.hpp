@@ -18,7 +18,9 @@ inline void probe_one(const uint8_t* p, int64_t len, bool raw, int32_t max_image
     d.status = DINO_IMG_CORRUPT;
     d.width = d.height = d.ncomp = 0;
   } else {
-    parse_jpeg(p, len, max_image_dim, &d, raw);
+    // a probe has no context: a four-component frame is parsed as a context with
+    // dino_ctx_set_four_component on would, and reported below as kind 3
+    parse_jpeg(p, len, max_image_dim, &d, raw, true);
     if (d.status == DINO_IMG_OK && d.kind == 1) {
       HostMarkerFinder find;
       if (prog_walk(p, len, &d, scans, find) == DINO_IMG_OK) {
@@ -30,13 +32,21 @@ inline void probe_one(const uint8_t* p, int64_t len, bool raw, int32_t max_image
       }
     }
   }
+  // Four components: status DINO_IMG_UNSUPPORTED whatever else the file is (what a context
+  // with the option off reports at the SOF marker), and kind 3 when a context with the option
+  // on decodes it; its workspace is counted then, so that a dino_reserve from these numbers
+  // covers it (a little too much for a context that hands the file over instead).
+  const bool four = d.ncomp == 4;
+  const bool counted = d.status == DINO_IMG_OK;
+  if (four) d.status = DINO_IMG_UNSUPPORTED;
   if (info_row) {
     info_row[0] = d.status;
     info_row[1] = d.status == DINO_IMG_OK || d.status > 0 ? d.width : 0;
     info_row[2] = d.status == DINO_IMG_OK || d.status > 0 ? d.height : 0;
-    info_row[3] = d.status == DINO_IMG_OK ? d.kind : -1;
+    info_row[3] = !counted ? -1 : (four ? 3 : d.kind);
   }
-  if (d.status != DINO_IMG_OK) return;
+  if (!counted) return;
+  d.status = DINO_IMG_OK;
   *ws += image_chunk_bytes(d).total();
   if (cfg) {
     for (int v = 0; v < cfg->n_global + cfg->n_local; ++v)

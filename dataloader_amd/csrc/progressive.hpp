@@ -130,13 +130,13 @@ DHD int prog_walk(const uint8_t* p, int64_t len, ImgDesc* d, ScanRec* scans, Fin
   int32_t dht[8];
   for (int i = 0; i < 8; ++i) dht[i] = d->huff_off[i];
   int32_t ri = d->restart_interval;
-  int8_t coef_bits[kMaxComp][10];     // coefficients 0..9 (what smoothing_ok reads), -1 = never coded
-  int8_t level_of[kMaxComp][64];      // last level that wrote (component, coefficient)
-  for (int c = 0; c < kMaxComp; ++c) {
+  int8_t coef_bits[kMaxFrameComp][10];     // coefficients 0..9 (what smoothing_ok reads), -1 = never coded
+  int8_t level_of[kMaxFrameComp][64];      // last level that wrote (component, coefficient)
+  for (int c = 0; c < kMaxFrameComp; ++c) {
     for (int k = 0; k < 10; ++k) coef_bits[c][k] = -1;
     for (int k = 0; k < 64; ++k) level_of[c][k] = -1;
   }
-  bool latched[kMaxComp] = {false, false, false};
+  bool latched[kMaxFrameComp] = {false, false, false, false};
   bool qt_redefined[4] = {false, false, false, false};
   int n = 0;
   int64_t pos = d->first_sos + 2;  // after the SOS marker code
@@ -573,18 +573,18 @@ DHD LdsTable sel4(const LdsTable* t, int k) { return k == 0 ? t[0] : (k == 1 ? t
 struct ScanGeom {
   int32_t mcus_x, mcus_y, bpm;
   uint32_t comp, bx, by, kk;
-  int32_t ch[kMaxComp], cv[kMaxComp];  // sampling factors, read with constant indices
-  int64_t plane[kMaxComp];             // coefficient plane offset (int16 units) and blocks per row
-  int32_t bw[kMaxComp];
+  int32_t ch[kMaxFrameComp], cv[kMaxFrameComp];  // sampling factors, read with constant indices
+  int64_t plane[kMaxFrameComp];            // coefficient plane offset (int16 units) and blocks per row
+  int32_t bw[kMaxFrameComp];
 };
 DHD int sg_field(uint32_t f, int b) { return (int)((f >> (2 * b)) & 3u); }
 template <typename T>
-DHD T sel3(const T* a, int c) { return c == 0 ? a[0] : (c == 1 ? a[1] : a[2]); }
+DHD T selc(const T* a, int c) { return c == 0 ? a[0] : (c == 1 ? a[1] : (c == 2 ? a[2] : a[3])); }
 
 DHD ScanGeom scan_geom(const ImgDesc& d, const ScanRec& sr) {
   ScanGeom g;
   g.comp = g.bx = g.by = g.kk = 0;
-  for (int c = 0; c < kMaxComp; ++c) {
+  for (int c = 0; c < kMaxFrameComp; ++c) {
     const CompDesc& cd = d.comp[c < d.ncomp ? c : 0];
     g.ch[c] = cd.h;
     g.cv[c] = cd.v;
@@ -627,10 +627,10 @@ DHD int16_t* scan_block(int16_t* coef, const ScanRec& sr, const ScanGeom& g, int
   *c = cc;
   int bx = mx, by = my;
   if (sr.ns != 1) {
-    bx = mx * sel3(g.ch, cc) + sg_field(g.bx, blk);
-    by = my * sel3(g.cv, cc) + sg_field(g.by, blk);
+    bx = mx * selc(g.ch, cc) + sg_field(g.bx, blk);
+    by = my * selc(g.cv, cc) + sg_field(g.by, blk);
   }
-  return coef + sel3(g.plane, cc) + ((int64_t)by * sel3(g.bw, cc) + bx) * 64;
+  return coef + selc(g.plane, cc) + ((int64_t)by * selc(g.bw, cc) + bx) * 64;
 }
 
 // AC refinement of one block (decode_mcu_AC_refine), on masks in zigzag order.

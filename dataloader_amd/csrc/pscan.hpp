@@ -495,7 +495,7 @@ DHD ScanGeom pscan_geom(D d, const ScanRec& sr) {
   g.comp = g.bx = g.by = g.kk = 0;
   const int ncomp = d->ncomp;
 #pragma unroll
-  for (int c = 0; c < kMaxComp; ++c) {
+  for (int c = 0; c < kMaxFrameComp; ++c) {
     const int cc = c < ncomp ? c : 0;
     g.ch[c] = d->comp[cc].h;
     g.cv[c] = d->comp[cc].v;
@@ -516,7 +516,7 @@ DHD ScanGeom pscan_geom(D d, const ScanRec& sr) {
     for (int k = 0; k < 4; ++k) {
       if (k >= sr.ns) break;
       const int ci = k == 0 ? sr.comp[0] : (k == 1 ? sr.comp[1] : (k == 2 ? sr.comp[2] : sr.comp[3]));
-      const int h = sel3(g.ch, ci), v = sel3(g.cv, ci);
+      const int h = selc(g.ch, ci), v = selc(g.cv, ci);
       for (int y = 0; y < v; ++y)
         for (int x = 0; x < h; ++x) {
           g.comp |= (uint32_t)ci << (2 * b);
@@ -537,10 +537,10 @@ DHD int64_t pscan_block_elem(const ScanRec& sr, const ScanGeom& g, int mx, int m
   const int cc = sg_field(g.comp, blk);
   int bx = mx, by = my;
   if (sr.ns != 1) {
-    bx = mx * sel3(g.ch, cc) + sg_field(g.bx, blk);
-    by = my * sel3(g.cv, cc) + sg_field(g.by, blk);
+    bx = mx * selc(g.ch, cc) + sg_field(g.bx, blk);
+    by = my * selc(g.cv, cc) + sg_field(g.by, blk);
   }
-  return sel3(g.plane, cc) + ((int64_t)by * sel3(g.bw, cc) + bx) * 64;
+  return selc(g.plane, cc) + ((int64_t)by * selc(g.bw, cc) + bx) * 64;
 }
 
 // One whole scan.  T: lookup(k, p, &sym, &len) for table position k of the scan (DC
@@ -558,7 +558,7 @@ DHD void pscan_decode(R& r, const T& t, D d, const ScanRec& sr, bool prog, Sink&
   const bool ac_refine = prog && ss > 0 && sr.ah > 0;
   const bool ac_first = prog && ss > 0 && sr.ah == 0;
   const bool dc_refine = prog && ss == 0 && sr.ah > 0;
-  if (ac_refine) sink.rbegin(sel3(g.plane, (int)g.comp), sel3(g.bw, (int)g.comp), g.mcus_x, g.mcus_y);
+  if (ac_refine) sink.rbegin(selc(g.plane, (int)g.comp), selc(g.bw, (int)g.comp), g.mcus_x, g.mcus_y);
   int64_t m = 0;
   for (int my = 0; my < g.mcus_y; ++my) {
     for (int mx = 0; mx < g.mcus_x; ++mx, ++m) {

@@ -66,6 +66,7 @@ class IngestEngine:
         self.stream = stream  # None: launch on torch's current stream
         self.prog_lanes: bool | None = None  # set_prog_decoder's choice (None: the library default)
         self.resample_filter = 0  # set_resample_filter's choice (DINO_FILTER_*; 0: bicubic)
+        self.four_component = False  # set_four_component's choice (False: CMYK / YCCK files report status 1)
 
     def _s(self) -> ctypes.c_void_p:
         return _stream_handle(self.device, self.stream)
@@ -138,6 +139,13 @@ class IngestEngine:
         code = resample_filter_code(f)
         _lib.check(self.lib.dino_ctx_set_resample_filter(self._ctx, code), "dino_ctx_set_resample_filter")
         self.resample_filter = code
+
+    def set_four_component(self, on: bool) -> None:
+        """Decode four-component (Adobe CMYK / YCCK) JPEGs on this context (``True``) to the RGB
+        Pillow's ``convert("RGB")`` gives, or report them ``DINO_IMG_UNSUPPORTED`` (``False``, the
+        default) from the next call on (``dino_ctx_set_four_component``)."""
+        _lib.check(self.lib.dino_ctx_set_four_component(self._ctx, int(bool(on))), "dino_ctx_set_four_component")
+        self.four_component = bool(on)
 
     def set_timing(self, enable: bool) -> None:
         _lib.check(self.lib.dino_set_timing(self._ctx, int(enable)), "dino_set_timing")

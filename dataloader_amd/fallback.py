@@ -3,15 +3,17 @@
 The reference decodes every image with Pillow (``Image.open(BytesIO(b)).convert("RGB")``,
 reference ``src/dino_loader/backends/cpu.py:251``).  The HIP decoder covers
 baseline, extended-sequential, progressive and multi-scan Huffman JPEGs
-(8-bit, 1 or 3 components); everything else it reports with a positive status
+(8-bit, 1 or 3 components, and with ``four_component="device"`` the 4-component
+Adobe CMYK / YCCK files); everything else it reports with a positive status
 (``include/dino_ingest.h``).  So that no image the reference would decode comes
 back as zeros, each host batch is screened *before* it is launched:
 
 1. ``dino_probe`` runs the device's own parser (and its progressive marker walk)
    on the host bytes — a few microseconds per image — and reports every image's
    status, plus the exact decode-workspace bytes and an augment-workspace bound;
-2. images with status ``DINO_IMG_UNSUPPORTED`` (CMYK/YCCK, arithmetic, lossless,
-   progressive files libjpeg would block-smooth, > 64 scans) are decoded here by
+2. images with status ``DINO_IMG_UNSUPPORTED`` (arithmetic, lossless, progressive
+   files libjpeg would block-smooth, > 64 scans, and CMYK / YCCK unless
+   ``four_component="device"``: see ``accept_four_component``) are decoded here by
    Pillow — the very call the reference makes — and travel to the GPU as
    pre-decoded RGB images (``DINO_RAW_MAGIC`` container); if Pillow raises, the
    image travels as zero bytes, which the device reports as corrupt and
@@ -35,6 +37,27 @@ from . import _lib
 
 IMG_UNSUPPORTED = 1
 IMG_LIMIT = 4
+KIND_MULTISCAN = 1
+KIND_FOUR_COMPONENT = 3  # dino_probe: status 1, decodable by a context with the four-component option on
+FOUR_COMPONENT_MODES = ("host", "device")
+
+
+def four_component_mask(info: np.ndarray) -> np.ndarray:
+    """Rows of a probed batch that are four-component (CMYK / YCCK) files a context with
+    ``dino_ctx_set_four_component`` on decodes (status 1, kind 3)."""
+    return (info[:, 0] == IMG_UNSUPPORTED) & (info[:, 3] == KIND_FOUR_COMPONENT)
+
+
+def accept_four_component(info: np.ndarray) -> np.ndarray:
+    """The probe's info as contexts with the four-component option on will decode the batch:
+    the rows of ``four_component_mask`` become status 0, kind 1 (such a file always takes the
+    coefficient-buffer path, so it is routed like any progressive image).  A copy; the
+    probe's workspace numbers already count these images."""
+    out = np.array(info, np.int32, copy=True)
+    m = four_component_mask(out)
+    out[m, 0] = 0
+    out[m, 3] = KIND_MULTISCAN
+    return out
 
 
 def decode_with_pillow(jpeg) -> np.ndarray | None:
@@ -123,13 +146,20 @@ def pillow_container(jpeg) -> bytes:
 
 
 def hand_over(jpegs: list, status: np.ndarray, mask: np.ndarray | None = None,
-              pool: "HostDecoder | None" = None) -> tuple[list, int, np.ndarray]:
+              pool: "HostDecoder | None" = None, four_component: str = "host",
+              kind: np.ndarray | None = None) -> tuple[list, int, np.ndarray]:
     """Replace the images the GPU decoder does not decode (``status`` ``IMG_UNSUPPORTED`` or
     ``IMG_LIMIT``, or ``mask`` when given) by Pillow-decoded raw RGB containers (zero bytes
-    where Pillow raises), in ``pool``'s worker processes when given.  Returns (new list,
-    images handed over, raw mask: uint8[B], 1 where the new entry is a container — the
-    mask dino_probe / dino_decode need to accept it)."""
-    idx = np.flatnonzero(np.isin(status, (IMG_UNSUPPORTED, IMG_LIMIT)) if mask is None else mask)
+    where Pillow raises), in ``pool``'s worker processes when given.  With ``four_component``
+    ``"device"`` and the probe's ``kind`` column, the four-component files the device decodes
+    (kind 3) stay as they are.  Returns (new list, images handed over, raw mask: uint8[B], 1
+    where the new entry is a container — the mask dino_probe / dino_decode need to accept it)."""
+    _check_four_component(four_component)
+    if mask is None:
+        mask = np.isin(status, (IMG_UNSUPPORTED, IMG_LIMIT))
+        if four_component == "device" and kind is not None:
+            mask &= ~((np.asarray(status) == IMG_UNSUPPORTED) & (np.asarray(kind) == KIND_FOUR_COMPONENT))
+    idx = np.flatnonzero(mask)
     out = list(jpegs)
     if pool is not None and len(idx) > 1:
         for i, f in zip(idx, [pool.submit(jpegs[i]) for i in idx]):
@@ -148,9 +178,18 @@ def raw_mask_of(images: list, handed) -> np.ndarray:
     return m
 
 
-def route_mask(info: np.ndarray, host_fallback: bool, multiscan_route: str, host_max: int) -> np.ndarray:
+def _check_four_component(mode: str) -> None:
+    if mode not in FOUR_COMPONENT_MODES:
+        raise ValueError(f"four_component must be 'host' or 'device', not {mode!r}")
+
+
+def route_mask(info: np.ndarray, host_fallback: bool, multiscan_route: str, host_max: int,
+               four_component: str = "host") -> np.ndarray:
     """Images of a probed batch to decode with Pillow on the host.
 
+    * with ``four_component`` ``"device"`` (contexts with ``dino_ctx_set_four_component`` on),
+      four-component files the device decodes (status 1, kind 3) count as coefficient-buffer
+      images below, not as unsupported ones; with ``"host"`` (default) they are handed over;
     * ``DINO_IMG_UNSUPPORTED`` images and JPEGs over a caller-chosen ``max_image_dim``
       (``DINO_IMG_LIMIT``), always (when ``host_fallback``);
     * coefficient-buffer images (``info[:, 3] == 1``: progressive, multi-scan sequential,
@@ -160,6 +199,9 @@ def route_mask(info: np.ndarray, host_fallback: bool, multiscan_route: str, host
       Pillow, ``"device"`` none, ``"auto"`` all of them when the batch has at most
       ``host_max`` (the host decodes ~6 ms per 640x480 image per worker, off the
       critical path when prepared one batch ahead), else none."""
+    _check_four_component(four_component)
+    if four_component == "device":
+        info = accept_four_component(info)
     mask = np.isin(info[:, 0], (IMG_UNSUPPORTED, IMG_LIMIT)) if host_fallback else np.zeros(len(info), bool)
     ms = (info[:, 0] == 0) & (info[:, 3] == 1)
     if multiscan_route == "host" or (multiscan_route == "auto" and 0 < ms.sum() <= host_max):
@@ -174,7 +216,8 @@ class HostDecoder:
     safe).  ``start()`` starts them eagerly (the backend-built pipeline does, so that a
     script whose spawned children cannot start — no ``if __name__ == "__main__":`` guard
     around the training loop — fails at construction, not at the first CMYK file
-    mid-epoch); otherwise they start with the first submitted image.  If the pool cannot
+    mid-epoch; ``MI355XBackend(four_component="device")`` keeps those files on the GPU);
+    otherwise they start with the first submitted image.  If the pool cannot
     start or breaks, the hand-over continues in this process (same bytes, slower) with a
     ``RuntimeWarning``."""
 

@@ -484,9 +484,15 @@ class MI355XAugPipeline:
                  view_names: list[str] | None = None, host_fallback: bool = True,
                  multiscan_route: str = "auto", host_workers: int | None = None,
                  multiscan_host_max: int | None = None, prefetch: int | None = None,
-                 start_host_pool: bool = False, side_ahead: int = 64, resample_filter=None):
+                 start_host_pool: bool = False, side_ahead: int = 64, resample_filter=None,
+                 four_component: str = "host"):
         self._source = source
         self._aug_cfg = aug_cfg
+        # four-component (CMYK / YCCK) JPEGs: "host" hands them to Pillow, "device" decodes them in
+        # the kernels (every slot and side context gets dino_ctx_set_four_component) and routes them
+        # like any coefficient-buffer image (fallback.route_mask)
+        fallback._check_four_component(four_component)
+        self._four_component = four_component
         # Pillow filter of every view's resize (None: bicubic, or what a passed-in engine has)
         self._resample_filter = None if resample_filter is None else resample_filter_code(resample_filter)
         self._batch_size = int(batch_size)
@@ -518,8 +524,9 @@ class MI355XAugPipeline:
         self._host_max = int(multiscan_host_max) if multiscan_host_max is not None else 8 * workers
         # per-image outcome of every batch handed over (status code -> images), images the
         # GPU decoder left to Pillow, and workspace regrowths
+        # four_component: CMYK / YCCK images kept on the device (four_component="device")
         self.stats = {"batches": 0, "images": 0, "status": Counter(), "host_decoded": 0, "reserves": 0,
-                      "side_decoded": 0}
+                      "side_decoded": 0, "four_component": 0}
         # host-side seconds per phase: pull / pack / probe (host half), wait (launch thread
         # waiting for the host half), launch (H2D copies + kernel enqueue)
         self.host_seconds = {"pull": 0.0, "pack": 0.0, "probe": 0.0, "wait": 0.0, "launch": 0.0}
@@ -576,6 +583,8 @@ class MI355XAugPipeline:
             # (the side contexts of progside.py only decode: the filter is not theirs to know)
             if self._resample_filter is not None:
                 eng.set_resample_filter(self._resample_filter)
+            if self._four_component == "device":
+                eng.set_four_component(True)
             self._slots.append(_Slot(eng))
         self._last: _Slot = self._slots[0]          # the last launched batch
         # output sets (shape key, tensors, consumer stream), batch n -> set n % (depth + 1)
@@ -743,6 +752,16 @@ class MI355XAugPipeline:
         Runs on the prefetch thread (or inline at prefetch 0)."""
         return self._pack_raw(self._pull_raw())
 
+    def _accept(self, info: np.ndarray, count: bool = True) -> np.ndarray:
+        """A probe's info as this pipeline's contexts decode the batch: with
+        ``four_component="device"`` the four-component rows become decodable coefficient-buffer
+        images (``fallback.accept_four_component``), counted in ``stats`` once per batch."""
+        if self._four_component != "device":
+            return info
+        if count:
+            self.stats["four_component"] += int(fallback.four_component_mask(info).sum())
+        return fallback.accept_four_component(info)
+
     def _pull_raw(self) -> tuple:
         """The pull half of ``_prepare_next``: the source's next batch as (spans batch or None,
         JPEG list or None, pointers, lengths, references keeping the bytes alive)."""
@@ -773,8 +792,11 @@ class MI355XAugPipeline:
             sizes = self._sizes()
             cfg = self._cfg(*sizes)
             t1 = time.perf_counter()
+            counted = False
             if bs is not None and bs.registered:
                 info, ws, aws = fallback.probe_spans(ptrs, lens, self._max_image_dim, cfg)
+                info = self._accept(info)
+                counted = True
                 if not fallback.route_mask(info, self._host_fallback, self._route, self._host_max).any():
                     st = self._ring.acquire()
                     st.fit(0, B)
@@ -788,6 +810,7 @@ class MI355XAugPipeline:
                 st.fit(int(lens.sum()), B)
                 off, info, ws, aws = fallback.gather_probe(ptrs, lens, st.buf, self._gather_threads,
                                                            self._max_image_dim, cfg)
+                info = self._accept(info, count=not counted)
                 st.off.numpy()[: B + 1] = off
                 hs["pack"] += time.perf_counter() - t1
                 if bs is not None:  # packed: the shard ranges are no longer read
@@ -827,6 +850,7 @@ class MI355XAugPipeline:
         fb = self._source.next_prepared(timeout=None if block else 0.0)
         if fb is None:
             return None
+        fb.info = self._accept(fb.info)
         mask = fallback.route_mask(fb.info, self._host_fallback, self._route, self._host_max)
         if not mask.any():
             return _Prepared(None, None, fb.offsets, fb.info, fb.ws, fb.aws, self._feed_sizes, {}, feed=fb)
@@ -879,7 +903,8 @@ class MI355XAugPipeline:
         if self._side is None:
             lanes, pool = progside.side_plan(self._side_ahead)
             self._side = progside.DeviceSideDecoder(self.device, max_images=pool, max_image_dim=self._max_image_dim,
-                                                    stream_set=self._stream_set, lanes=lanes)
+                                                    stream_set=self._stream_set, lanes=lanes,
+                                                    four_component=self._four_component == "device")
             self.stats["side_lanes"] = lanes
         if pb.jpegs is not None:
             imgs = {int(i): pb.jpegs[i] for i in idx}
@@ -1070,6 +1095,7 @@ class MI355XAugPipeline:
             st.mask.numpy()[:B] = rm
             raw = st.mask[:B]
             pb.info, ws, aws = fallback.probe(st.buf.data_ptr(), off, B, self._max_image_dim, cfg, rm)
+            pb.info = self._accept(pb.info, count=False)
             nbytes = int(off[-1])
         else:
             nbytes = int(pb.offsets[-1])

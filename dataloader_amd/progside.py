@@ -126,13 +126,16 @@ class _SideEngine:
     Consecutive launches of a context are ordered by the dedicated stream itself."""
 
     def __init__(self, device: torch.device, max_images: int, max_image_dim: int, cu_count: int = 0,
-                 dedicated: bool = True, index: int = 0, stream_set: int = 0, lanes: bool = False):
+                 dedicated: bool = True, index: int = 0, stream_set: int = 0, lanes: bool = False,
+                 four_component: bool = False):
         from .pipeline import role_stream
         self.raw = _create_stream(device.index or 0, int(cu_count)) if dedicated else None
         self.stream = self.raw if dedicated else role_stream(device, "side", index, stream_set)
         self.eng = IngestEngine(device, max_batch=max_images, max_views=1, max_crop_size=8,
                                 max_image_dim=max_image_dim, workspace_bytes=64 << 20, stream=self.stream)
         self.eng.set_prog_decoder(lanes)
+        if four_component:  # CMYK / YCCK files join the pools (the lane decoder leaves them to the wave decoder)
+            self.eng.set_four_component(True)
         self.copy = role_stream(device, "side_copy", index, stream_set)  # this context's torch stream (allocations, copies)
         self.last: torch.cuda.Event | None = None   # the engine's workspace is free once this completes
         self.keep = None                             # host / device inputs of the mini-batch in flight
@@ -191,7 +194,8 @@ class DeviceSideDecoder:
     thread they cost the c2_prog leg ~3 ms per batch (``scripts/prof_leg.py``)."""
 
     def __init__(self, device: torch.device, max_images: int = WAVE_POOL, min_images: int | None = None,
-                 engines: int | None = None, max_image_dim: int = 0, stream_set: int = 0, lanes: bool = False):
+                 engines: int | None = None, max_image_dim: int = 0, stream_set: int = 0, lanes: bool = False,
+                 four_component: bool = False):
         import os
         # measured (scripts/route_study.py, 16 progressive per 256-image batch, dedicated queues,
         # look-ahead 64, profiles/r03_side_pools.jsonl): pools of 16 images on 2 contexts 11.2k img/s,
@@ -212,6 +216,7 @@ class DeviceSideDecoder:
         self.max_image_dim = int(max_image_dim)
         self.stream_set = int(stream_set)  # the owning pipeline's role streams (pipeline.acquire_stream_set)
         self.lanes = bool(lanes)           # the side contexts' decoder (side_plan)
+        self.four_component = bool(four_component)  # the side contexts decode CMYK / YCCK files
         self.lane_min = int(os.environ.get("DINO_SIDE_LANE_MIN", LANE_MIN_POOL))  # smaller pools: wave decoder
         self._engines: list[_SideEngine] = []
         self._rr = 0
@@ -257,7 +262,8 @@ class DeviceSideDecoder:
                 return e
         if len(self._engines) < self.cap:
             e = _SideEngine(self.device, self.max_images, self.max_image_dim, self.cu_count, self.dedicated,
-                            index=len(self._engines), stream_set=self.stream_set, lanes=self.lanes)
+                            index=len(self._engines), stream_set=self.stream_set, lanes=self.lanes,
+                            four_component=self.four_component)
             self._engines.append(e)
             return e
         e = self._engines[self._rr % len(self._engines)]
@@ -310,6 +316,8 @@ class DeviceSideDecoder:
         t2 = time.perf_counter()
         ph["pack"] += t2 - t1
         info, ws, _ = fallback.probe(hb.data_ptr(), off.numpy(), len(items), self.max_image_dim)
+        if self.four_component:
+            info = fallback.accept_four_component(info)
         t3 = time.perf_counter()
         ph["probe"] += t3 - t2
         eng.reserve(ws, 0)

@@ -47,7 +47,8 @@
  *    progressive images per context), dino_copy_rgb_packed (a pool's images into one
  *    buffer in one launch).  Still additive within ABI 4: dino_ctx_set_resample_filter
  *    (Pillow's BILINEAR / BOX / HAMMING / LANCZOS per context; BICUBIC stays the default)
- *    and dino_resample_coeffs_host.
+ *    and dino_resample_coeffs_host; dino_ctx_set_four_component (four-component Adobe CMYK /
+ *    YCCK JPEGs decoded on the device, off by default) and kind 3 in the probes' info.
  */
 #ifndef DINO_INGEST_H
 #define DINO_INGEST_H
@@ -78,8 +79,9 @@ extern "C" {
 #define DINO_IMG_TRUNCATED (-2)      /* entropy data ends before the last MCU, no EOI */
 #define DINO_IMG_BADDATA (-3)        /* libjpeg would error (bad sampling, MCU too large) */
 #define DINO_IMG_TOO_LARGE (-4)      /* > 2 x PIL.Image.MAX_IMAGE_PIXELS: Pillow raises DecompressionBombError */
-#define DINO_IMG_UNSUPPORTED 1       /* arithmetic / lossless / hierarchical / >8-bit / CMYK / 2-component,
-                                        progressive needing libjpeg block smoothing, > DINO_MAX_SCANS scans */
+#define DINO_IMG_UNSUPPORTED 1       /* arithmetic / lossless / hierarchical / >8-bit / 2-component,
+                                        progressive needing libjpeg block smoothing, > DINO_MAX_SCANS scans,
+                                        four-component (CMYK / YCCK) unless dino_ctx_set_four_component is on */
 #define DINO_IMG_MULTISCAN 2         /* (ABI v1; no longer produced: multi-scan files are decoded) */
 #define DINO_IMG_NO_SPACE 3          /* the ctx workspace could not hold the image or one of its views
                                         (dino_reserve more and run again) */
@@ -236,7 +238,12 @@ int dino_batch_info(dino_ctx* ctx, int32_t* d_info, void* stream);
 /* Host pre-screen of a batch held in HOST memory (same packing as dino_decode): runs
  * the device parser (and, for progressive / multi-scan files, its marker walk) on
  * the CPU.  info (nullable): int32[batch][4] = {status the device decode will report,
- * width, height, kind (0 baseline, 1 multi-scan, 2 raw RGB, -1 failed)}.  ws_need:
+ * width, height, kind (0 baseline, 1 multi-scan, 2 raw RGB, 3 four-component, -1 failed)}.
+ * A probe has no context, so a four-component (CMYK / YCCK) file always has status
+ * DINO_IMG_UNSUPPORTED here; kind 3 says that a context with dino_ctx_set_four_component on
+ * decodes it (as a multi-scan image), and its decode workspace and views are counted in
+ * ws_need / aws_need so that a dino_reserve from them covers that decode (for a context that
+ * hands the file over instead, this over-reserves by the file's coefficient buffer).  ws_need:
  * decode workspace bytes the batch needs; aws_need: an upper bound of the augment
  * workspace for cfg's views (0 when cfg is NULL).  Images with status > 0 are the
  * ones the caller should decode itself and pass as raw RGB (DINO_RAW_MAGIC).
@@ -338,6 +345,15 @@ int dino_ctx_set_prog_decoder(dino_ctx* ctx, int32_t decoder);
 #define DINO_FILTER_HAMMING 3
 #define DINO_FILTER_LANCZOS 4
 int dino_ctx_set_resample_filter(dino_ctx* ctx, int32_t filter);
+
+/* Four-component JPEGs (8-bit Huffman SOF0/1/2 with Adobe CMYK or YCCK data) on this ctx,
+ * from the next call on: 0 (default) reports them DINO_IMG_UNSUPPORTED, for the caller to
+ * decode; non-zero decodes them on the device to the RGB of Pillow's
+ * Image.open(..).convert("RGB"), bit for bit (libjpeg's YCCK -> CMYK step, Pillow's
+ * inverted "CMYK;I" read and its cmyk2rgb).  Such a file always takes the coefficient-buffer
+ * path (kind 1), a baseline file of one interleaved scan included, so it costs a progressive
+ * file's latency.  No reference counterpart: Pillow decodes them on a CPU thread (cpu.py:251). */
+int dino_ctx_set_four_component(dino_ctx* ctx, int32_t on);
 
 /* The coefficient code of the resample kernels run on the host (no GPU involved; tests and
  * introspection): for in_size -> out_size with `filter`, *ksize = taps reserved per output;
