@@ -18,6 +18,16 @@ from .params import (OUT_BF16, OUT_FP8_E4M3, OUT_FP32, VIEW_PARAMS_DTYPE, DinoLi
                      resample_filter_code)
 
 _TORCH_OUT = {OUT_BF16: torch.bfloat16, OUT_FP32: torch.float32, OUT_FP8_E4M3: torch.float8_e4m3fn}
+_DTYPES = {"bf16": OUT_BF16, "fp32": OUT_FP32, "fp8": OUT_FP8_E4M3}
+
+
+def _out_code(out_dtype) -> int:
+    """A pipeline's ``out_dtype`` argument (an OUT_* code, a torch dtype or a name) as its OUT_* code."""
+    if isinstance(out_dtype, int):
+        return out_dtype
+    if isinstance(out_dtype, torch.dtype):
+        return {torch.bfloat16: OUT_BF16, torch.float32: OUT_FP32, torch.float8_e4m3fn: OUT_FP8_E4M3}[out_dtype]
+    return _DTYPES.get(out_dtype, OUT_BF16)
 
 
 def _ptr(t: torch.Tensor) -> ctypes.c_void_p:

@@ -24,16 +24,12 @@ have decoded but that came back zero-filled raises a ``RuntimeWarning``.
 
 from __future__ import annotations
 
-import atexit
 import ctypes
 import itertools
 import os
-import queue
 import sys
-import threading
 import time
 import warnings
-import weakref
 from collections import Counter, deque
 from typing import Any
 
@@ -41,18 +37,13 @@ import numpy as np
 import torch
 
 from . import fallback
-from .engine import IngestEngine, pack_jpegs, params_from_device
-from .params import OUT_BF16, OUT_FP8_E4M3, OUT_FP32, RECORD_BYTES, make_aug_config, resample_filter_code
-
-_DTYPES = {"bf16": OUT_BF16, "fp32": OUT_FP32, "fp8": OUT_FP8_E4M3}
-
-
-def _out_code(out_dtype) -> int:
-    if isinstance(out_dtype, int):
-        return out_dtype
-    if isinstance(out_dtype, torch.dtype):
-        return {torch.bfloat16: OUT_BF16, torch.float32: OUT_FP32, torch.float8_e4m3fn: OUT_FP8_E4M3}[out_dtype]
-    return _DTYPES.get(out_dtype, OUT_BF16)
+from .engine import IngestEngine, _out_code, params_from_device
+from .params import RECORD_BYTES, make_aug_config, resample_filter_code
+# what moved out of this module stays importable from it (the same objects)
+from .staging import PACK_THREADS, RAW_AHEAD, _Prefetcher, _Prepared, _StagingRing
+from .streams import (_LIVE, _RAW_ROLE_STREAMS, _ROLE_STREAMS, acquire_stream_set,  # noqa: F401
+                      release_role_streams, release_stream_set, role_stream)
+from .useraug import MI355XUserAugIterator, MI355XUserAugPipeline, resize_scratch_bound  # noqa: F401
 
 
 def _refcounts(views) -> list[int]:
@@ -116,354 +107,6 @@ class _Slot:
         self.buf_done: list = [None, None]            # event after the last batch that read each buffer
         self.buf_next = 0
         self.view_set = -1                            # the output set (pipeline ring) of the slot's batch
-
-
-class _Staging:
-    """A pinned host buffer the batch's JPEG bytes (+ int64 offsets + raw mask) are packed
-    into before the H2D copy.  Owned by the host half while it is being filled and until the
-    launch that copies it out has retired (``released`` event)."""
-
-    def __init__(self):
-        self.buf: torch.Tensor | None = None
-        self.off: torch.Tensor | None = None
-        self.lens: torch.Tensor | None = None
-        self.mask: torch.Tensor | None = None
-        self.released: torch.cuda.Event | None = None
-        self.busy = False
-
-    def fit(self, nbytes: int, n: int) -> None:
-        if nbytes > 0 and (self.buf is None or self.buf.numel() < nbytes):
-            self.buf = torch.empty(max(nbytes, 1) * 5 // 4 + 64, dtype=torch.uint8, pin_memory=True)
-        if self.off is None or self.off.numel() < n + 1:
-            self.off = torch.empty(n + 1, dtype=torch.int64, pin_memory=True)
-            self.lens = torch.empty(n, dtype=torch.int64, pin_memory=True)
-            self.mask = torch.empty(n, dtype=torch.uint8, pin_memory=True)
-
-
-class _StagingRing:
-    """Round-robin staging buffers shared by the host half (fills) and the launch (frees)."""
-
-    def __init__(self, n: int):
-        self._bufs = [_Staging() for _ in range(max(2, n))]
-        self._next = 0
-        self._cv = threading.Condition()
-        self._closed = False
-
-    def close(self) -> None:
-        with self._cv:
-            self._closed = True
-            self._cv.notify_all()
-
-    def acquire(self) -> _Staging:
-        with self._cv:
-            st = self._bufs[self._next]
-            self._next = (self._next + 1) % len(self._bufs)
-            while st.busy and not self._closed:  # still waiting to be launched (rare: the ring is sized for it)
-                self._cv.wait()
-            if self._closed:
-                raise RuntimeError("MI355XAugPipeline closed")
-            st.busy = True
-        if st.released is not None:
-            st.released.synchronize()  # the H2D copy of its previous batch retired
-            st.released = None
-        return st
-
-    def release(self, st: _Staging, event: torch.cuda.Event | None) -> None:
-        with self._cv:
-            st.released = event
-            st.busy = False
-            self._cv.notify_all()
-
-
-class _Prepared:
-    """A pulled, packed and probed host batch whose host-routed images are decoding in the pool."""
-
-    def __init__(self, staging: _Staging, jpegs, offsets: np.ndarray, info: np.ndarray, ws: int, aws: int,
-                 sizes: tuple[int, int], futures: dict, spans=None, feed=None):
-        self.staging = staging        # None: no Python staging (native feed slot, or not yet needed)
-        self.spans = spans            # tario.BatchSpans: the batch stays in its page-locked shard ranges
-        self.feed = feed              # tario.FeedBatch: the batch is packed in a native feed slot
-        self.side = None              # progside.SideJob: its coefficient-buffer images, decoded ahead
-        self.room: dict = {}          # batch index -> offset of room for its container in the HBM copy
-        self.side_submitted = False   # _side_submit ran (on the prefetch thread, or at the pull)
-        self.jpegs = jpegs            # the source's list (None for the native feed)
-        self.offsets = offsets
-        self.info = info
-        self.ws, self.aws = ws, aws
-        self.sizes = sizes            # (G, L) the augment-workspace bound was computed for
-        self.futures = futures
-        # side look-ahead: the batch's input copied to HBM when it entered the look-ahead (its
-        # pinned staging / feed slot / shard ranges are free again); ready after `copied`
-        self.dev = None               # (d_bytes, d_offsets, d_lens or None)
-        self.lens = None              # host image lengths of a spans batch staged on the device
-        self.copied: torch.cuda.Event | None = None
-
-
-_END = object()
-# open pipelines, closed at interpreter exit before torch tears down: a prefetch thread must
-# not hold pinned tensors while the interpreter finalises them
-_LIVE: "weakref.WeakSet[MI355XAugPipeline]" = weakref.WeakSet()
-
-# One torch stream per (device, role, index) for the life of the process: every pipeline
-# reuses the streams of the first one.  HIP multiplexes streams onto a few hardware queues
-# (GPU_MAX_HW_QUEUES, 4 by default) in creation order, so fresh streams for each pipeline
-# land on other queues than the first pipeline's did, and a second side-route pipeline in
-# a process ran at 68-70k img/s against 101k for the first (profiles/r04_side_repeat_*).
-# The first request on a device takes the usual roles' streams in one fixed order (the
-# order a feed-driven side-route pipeline asks for them), so the mapping does not depend
-# on which kind of pipeline a process builds first.
-#
-# A set of role streams belongs to one live pipeline at a time (ADVICE r4): pipelines alive
-# together (train + val loaders) take different sets, so one's kernels never queue behind the
-# other's on a shared stream; a set is handed to the next pipeline once its owner closes.
-_ROLE_STREAMS: dict = {}
-_ROLE_LOCK = threading.Lock()
-_ROLE_ORDER = (("copy", 0), ("slot", 0), ("slot", 1), ("slot", 2), ("side_copy", 0), ("side_copy", 1))
-_SETS_BUSY: dict = {}   # device index -> stream-set ids held by live pipelines
-
-
-def _dev_index(device) -> int:
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-    return dev.index if dev.index is not None else torch.cuda.current_device()
-
-
-def acquire_stream_set(device) -> int:
-    """The lowest stream-set id no live pipeline on ``device`` holds (released by ``close``)."""
-    idx = _dev_index(device)
-    with _ROLE_LOCK:
-        busy = _SETS_BUSY.setdefault(idx, set())
-        s = 0
-        while s in busy:
-            s += 1
-        busy.add(s)
-        return s
-
-
-def release_stream_set(device, s: int) -> None:
-    with _ROLE_LOCK:
-        _SETS_BUSY.get(_dev_index(device), set()).discard(s)
-
-
-_RAW_ROLE_STREAMS: list = []  # (device, handle) of the role streams dino_stream_create made
-
-
-def _new_role_stream(idx: int, role: str) -> torch.cuda.Stream:
-    """A role's stream.  The batch slots and the copy stream come from the least priority's
-    pool of hardware queues (``dino_stream_create(-1)``), the other roles from torch's pool
-    (DINO_ROLE_STREAMS=torch: all of them).  HIP multiplexes streams onto GPU_MAX_HW_QUEUES
-    = 4 queues per priority; from torch's pool two of the three slots shared one and ran one
-    after the other (their batches queue in one FIFO: 128 of 198 e2e batches started on the
-    other slot's end), e2e 156.3k img/s; on queues of their own 172.9k (C2 177.2k,
-    ``scripts/rolestream_study.sh``).  The streams live as long as the process, as torch's
-    pool streams do."""
-    if role in ("slot", "copy") and os.environ.get("DINO_ROLE_STREAMS", "low") == "low":
-        from . import _lib
-        h = ctypes.c_void_p()
-        _lib.check(_lib.load().dino_stream_create(idx, -1, ctypes.byref(h)), "dino_stream_create")
-        _RAW_ROLE_STREAMS.append((idx, h.value))
-        return torch.cuda.ExternalStream(h.value, device=torch.device("cuda", idx))
-    return torch.cuda.Stream(device=idx)
-
-
-def role_stream(device, role: str, k: int = 0, stream_set: int = 0) -> torch.cuda.Stream:
-    idx = _dev_index(device)
-    with _ROLE_LOCK:
-        if not any(key[:2] == (idx, stream_set) for key in _ROLE_STREAMS):
-            for r, j in _ROLE_ORDER:
-                _ROLE_STREAMS[(idx, stream_set, r, j)] = _new_role_stream(idx, r)
-        st = _ROLE_STREAMS.get((idx, stream_set, role, k))
-        if st is None:
-            st = _ROLE_STREAMS[(idx, stream_set, role, k)] = _new_role_stream(idx, role)
-        return st
-
-
-@atexit.register
-def _close_live() -> None:
-    """At interpreter exit, before any library is finalized: close the open pipelines, then
-    destroy the role streams this module created with dino_stream_create (after the device is
-    idle and torch's allocator has retired its blocks' stream events), so that no stream of
-    ours is still alive when the HIP runtime and a profiler's tool library tear down (VERDICT r5
-    weak #6: an intermittent SIGSEGV in __cxa_finalize after a rocprofv3 run printed its line)."""
-    for p in list(_LIVE):
-        try:
-            p.close()
-        except Exception:  # noqa: BLE001
-            pass
-    release_role_streams()
-
-
-def release_role_streams() -> None:
-    """Destroy every role stream made by dino_stream_create (process exit; no pipeline may be
-    open).  Later role_stream() calls make new ones."""
-    if not _RAW_ROLE_STREAMS or _LIVE:
-        return
-    try:
-        from . import _lib
-        lib = _lib.load()
-        for dev in {d for d, _ in _RAW_ROLE_STREAMS}:
-            torch.cuda.synchronize(dev)
-        torch.cuda.empty_cache()
-        with _ROLE_LOCK:
-            for key in [k for k, st in _ROLE_STREAMS.items() if isinstance(st, torch.cuda.ExternalStream)]:
-                del _ROLE_STREAMS[key]
-            while _RAW_ROLE_STREAMS:
-                _, h = _RAW_ROLE_STREAMS.pop()
-                lib.dino_stream_destroy(ctypes.c_void_p(h))
-    except Exception:  # noqa: BLE001 - exit path: never raise
-        pass
-
-
-RAW_AHEAD = 2  # pulled, not yet packed batches the prefetcher's puller thread holds (list sources)
-# pack threads of a list source's prefetcher (DINO_PACK_THREADS): two measured no faster than
-# one on c2_prog (the packs then contend for the job's CPU share, profiles/r06_side_plan/r6x)
-PACK_THREADS = 1
-
-
-class _Prefetcher:
-    """The host half of the pipeline on worker threads (DALI's prefetch queue, reference
-    pipeline.py:317 ``prefetch_queue_depth``): pull the next batch from the source, pack it
-    into pinned staging (``dino_gather``), ``dino_probe`` it and submit its Pillow
-    hand-overs, up to ``ahead`` batches ahead of the launches.  The GIL is released inside
-    the native calls, so this overlaps the launch thread and the GPU.
-
-    For a source that hands over JPEG lists (the reference's ``_ReaderAdapter``) the pull
-    runs on a thread of its own, up to ``RAW_AHEAD`` batches ahead, and ``PACK_THREADS``
-    threads pack the pulled batches: the source's Python call and the native pack overlap
-    instead of adding up (c2_prog: ~0.8 ms pull + 1.2-3 ms pack per batch).
-    Batches are handed out in the source's order (sequence numbers, a reorder buffer of at
-    most ``ahead`` batches); the source's end and its errors arrive in place."""
-
-    def __init__(self, pipe: "MI355XAugPipeline", ahead: int):
-        self._pipe = pipe
-        self._ahead = max(1, ahead)
-        self._stop = threading.Event()
-        self.finished = False       # the source raised StopIteration (the END marker is queued)
-        self._cv = threading.Condition()
-        self._out: dict = {}        # sequence number -> _Prepared, _END or an exception
-        self._next = 0              # sequence number get() hands out next
-        self._raw: queue.Queue | None = None
-        self._threads: list[threading.Thread] = []
-        if not pipe._spans_feed and not pipe._native:
-            self._raw = queue.Queue(maxsize=RAW_AHEAD)
-            n = max(1, int(os.environ.get("DINO_PACK_THREADS", PACK_THREADS)))
-            self._threads.append(threading.Thread(target=self._pull_loop, name="dino-pull", daemon=True))
-            self._threads += [threading.Thread(target=self._pack_loop, name=f"dino-prefetch-{k}", daemon=True)
-                              for k in range(n)]
-        else:
-            self._threads.append(threading.Thread(target=self._run, name="dino-prefetch", daemon=True))
-        for t in self._threads:
-            t.start()
-
-    # ---- producers
-    def _emit(self, seq: int, item) -> bool:
-        """Place item `seq` in the reorder buffer once it is within `ahead` of the next hand-out."""
-        with self._cv:
-            while seq - self._next >= self._ahead and not self._stop.is_set():
-                self._cv.wait(0.1)
-            if self._stop.is_set():
-                return False
-            self._out[seq] = item
-            self._cv.notify_all()
-            return True
-
-    def _settle(self, seq: int, item) -> bool:
-        """Emit a prepared batch, or drop it if the prefetcher is closing."""
-        if isinstance(item, _Prepared) and not self._emit(seq, item):
-            self._pipe._drop(item)
-            return False
-        return isinstance(item, _Prepared) or self._emit(seq, item)
-
-    def _run(self) -> None:  # one thread pulls and packs (spans / native sources)
-        seq = 0
-        try:
-            while not self._stop.is_set():
-                pb = self._pipe._prepare_next()
-                self._pipe._stage_early(pb)
-                if not self._settle(seq, pb):
-                    return
-                seq += 1
-        except StopIteration:
-            self.finished = True
-            self._emit(seq, _END)
-        except BaseException as e:  # noqa: BLE001 - handed to the launch thread
-            self._emit(seq, e)
-
-    def _put_raw(self, item) -> bool:
-        while not self._stop.is_set():
-            try:
-                self._raw.put(item, timeout=0.1)
-                return True
-            except queue.Full:
-                continue
-        return False
-
-    def _pull_loop(self) -> None:
-        seq = 0
-        try:
-            while not self._stop.is_set():
-                if not self._put_raw((seq, self._pipe._pull_raw())):
-                    return
-                seq += 1
-        except StopIteration:
-            self._put_raw((seq, _END))
-        except BaseException as e:  # noqa: BLE001 - handed to a pack thread, then the launch thread
-            self._put_raw((seq, e))
-
-    def _pack_loop(self) -> None:
-        while not self._stop.is_set():
-            try:
-                seq, raw = self._raw.get(timeout=0.1)
-            except queue.Empty:
-                continue
-            if raw is _END or isinstance(raw, BaseException):
-                if raw is _END:
-                    self.finished = True
-                self._put_raw((seq, raw))  # the other pack threads see the end too
-                self._emit(seq, raw)
-                return
-            try:
-                pb = self._pipe._pack_raw(raw)
-                self._pipe._stage_early(pb)
-            except BaseException as e:  # noqa: BLE001 - handed to the launch thread in place
-                self._emit(seq, e)
-                continue
-            if not self._settle(seq, pb):
-                return
-
-    # ---- consumer
-    def get(self, block: bool = True) -> _Prepared | None:
-        with self._cv:
-            while self._next not in self._out:
-                if not block or self._stop.is_set():
-                    return None
-                self._cv.wait(0.1)
-            item = self._out[self._next]
-            if item is not _END and not isinstance(item, BaseException):
-                del self._out[self._next]
-                self._next += 1
-                self._cv.notify_all()
-        if item is _END:
-            raise StopIteration
-        if isinstance(item, BaseException):
-            raise item
-        return item
-
-    def close(self) -> None:
-        self._stop.set()
-        with self._cv:
-            self._cv.notify_all()
-        for t in self._threads:
-            t.join(timeout=5.0)
-        with self._cv:  # free staging of batches never launched
-            items, self._out = list(self._out.values()), {}
-        for item in items:
-            if isinstance(item, _Prepared):
-                self._pipe._drop(item)
-        while self._raw is not None:
-            try:
-                self._raw.get_nowait()
-            except queue.Empty:
-                break
 
 
 SIDE_URGENT_SHORT = 8  # side look-ahead batches flushed at once while the look-ahead is short (_pull_side)
@@ -593,6 +236,7 @@ class MI355XAugPipeline:
         # study hook (DINO_TIMELINE=1): per batch, host stamps and timing events on the copy and
         # slot streams (``timeline()``); off, nothing is recorded
         self._timeline: list | None = [] if os.environ.get("DINO_TIMELINE") == "1" else None
+        self._tl: dict | None = None                 # the record of the batch being enqueued
         if self._feed:
             sizes = self._sizes()
             self._feed_sizes = sizes
@@ -1135,127 +779,160 @@ class MI355XAugPipeline:
         self._tl_pull = time.perf_counter()
         return self._enqueue_prepared(self._pull())
 
+    def _tl_event(self, name: str, stream, stamp: str | None = None) -> None:
+        """Study hook (DINO_TIMELINE=1; off, nothing happens): a timing event ``name`` on
+        ``stream`` in the batch's timeline record, after the host clock under ``stamp``."""
+        if self._timeline is None:
+            return
+        if stamp is not None:
+            self._tl[stamp] = time.perf_counter()
+        self._tl[name] = torch.cuda.Event(enable_timing=True)
+        self._tl[name].record(stream)
+
+    def _tl_done(self, sl: _Slot) -> None:
+        """Study hook: the batch is launched; its record joins the timeline."""
+        if self._timeline is None:
+            return
+        self._tl_event("k1", sl.engine.stream)
+        self._tl["t1"] = time.perf_counter()
+        self._tl["slot"] = self._slots.index(sl)
+        self._timeline.append(self._tl)
+
     def _enqueue_prepared(self, pb: _Prepared) -> _Slot:
         if self._closed:
             self._drop(pb)
             raise RuntimeError("MI355XAugPipeline.run_one_batch() called after close()")
-        st = pb.staging
         t0 = time.perf_counter()
-        tl = {"t0": t0, "pull": getattr(self, "_tl_pull", t0)} if self._timeline is not None else None
-        copied = None
-        buf_j = None  # the native feed's input buffer of the slot this batch reads
+        self._tl = {"t0": t0, "pull": getattr(self, "_tl_pull", t0)} if self._timeline is not None else None
+        copied = None  # after the batch's uploads: what it held on the host is free once this completes
+        launched = False
         try:
             sl = self._next_slot()
             sizes = self._sizes()
             cfg = self._cfg(*sizes)
             host_buf, host_off, nbytes, raw = self._screen(sl, pb, cfg, sizes)
             B = len(pb.offsets) - 1
-            d_lens = None
             with sl.engine.on_stream():
-                if pb.dev is not None:  # copied to HBM when it joined the side look-ahead
-                    cur = torch.cuda.current_stream(self.device)
-                    cur.wait_event(pb.copied)
-                    d_bytes, d_offsets, d_lens = pb.dev
-                    for t in pb.dev:
-                        if t is not None:
-                            t.record_stream(cur)
-                elif pb.feed is not None:  # the native feed's pinned slot: bytes + offsets in two DMAs
-                    fb, pb.feed = pb.feed, None
-                    j = sl.buf_next
-                    sl.buf_next ^= 1
-                    if sl.d_ins[j] is None or sl.d_ins[j].numel() < fb.nbytes + 64:
-                        if sl.buf_done[j] is not None:  # the old buffer's last reader must finish first
-                            sl.buf_done[j].synchronize()
-                        sl.d_ins[j] = torch.empty(max(fb.nbytes, 1) * 9 // 8 + 64, dtype=torch.uint8,
-                                                  device=self.device)
-                    if sl.d_offs[j] is None or sl.d_offs[j].numel() < B + 1:
-                        if sl.buf_done[j] is not None:
-                            sl.buf_done[j].synchronize()
-                        sl.d_offs[j] = torch.empty(B + 1, dtype=torch.int64, device=self.device)
-                    cs = self._copy_stream if self._copy_stream is not None else sl.engine.stream
-                    try:
-                        if cs is not sl.engine.stream and sl.buf_done[j] is not None:
-                            cs.wait_event(sl.buf_done[j])
-                        if tl is not None:
-                            tl["issue"] = time.perf_counter()
-                            tl["c0"] = torch.cuda.Event(enable_timing=True)
-                            tl["c0"].record(cs)
-                        self._source.copy(fb, sl.d_ins[j].data_ptr(), sl.d_offs[j].data_ptr(),
-                                          cs.cuda_stream if cs is not None else 0)
-                        if tl is not None:
-                            tl["c1"] = torch.cuda.Event(enable_timing=True)
-                            tl["c1"].record(cs)
-                    except BaseException:
-                        self._source.release(fb)
-                        raise
-                    if cs is not sl.engine.stream:
-                        arrived = torch.cuda.Event()
-                        arrived.record(cs)
-                        torch.cuda.current_stream(self.device).wait_event(arrived)
-                    d_bytes, d_offsets = sl.d_ins[j], sl.d_offs[j][: B + 1]
-                    buf_j = j
-                elif pb.spans is not None:  # DMA the batch's shard ranges as they lie (no host copy)
-                    nbytes = int(pb.spans.offsets[-1])
-                    if sl.d_in is None or sl.d_in.numel() < nbytes:
-                        sl.d_in = torch.empty(max(nbytes, 1) * 9 // 8 + 64, dtype=torch.uint8, device=self.device)
-                    pos = 0
-                    for addr, n in pb.spans.parts:
-                        sl.engine.copy_from_host(sl.d_in, pos, addr, n)
-                        pos += n
-                    d_bytes = sl.d_in
-                    d_lens = st.lens[:B].to(self.device, non_blocking=True)
-                else:
-                    d_bytes = host_buf[:max(nbytes, 1)].to(self.device, non_blocking=True)
-                if host_off is not None and pb.dev is None:
-                    d_offsets = host_off.to(self.device, non_blocking=True)
+                d_bytes, d_offsets, d_lens, buf_j = self._upload(sl, pb, host_buf, host_off, nbytes, B)
                 d_raw = raw.to(self.device, non_blocking=True) if raw is not None else None
-                side = None
-                if pb.side is not None:  # coefficient-buffer images decoded ahead: their containers
-                    if pb.side.pending:  # still in the side pool: decode it now
-                        self._side.flush()
-                    conts = pb.side.ready()
-                    if conts:
-                        tm = time.perf_counter()
-                        base = host_off.numpy() if host_off is not None else pb.offsets
-                        # image lengths: the spans form's own (its offsets point into shard
-                        # ranges, the gaps hold tar headers and sidecars); packed: the gaps
-                        base_lens = pb.spans.lens if pb.spans is not None else \
-                            pb.lens if pb.lens is not None else np.diff(base[: B + 1])
-                        d_bytes, d_offsets, d_lens, d_raw = self._merge_side(
-                            pb.side, conts, d_bytes, int(base[B]), base, base_lens, raw, B)
-                        side = conts
-                        self.stats["side_decoded"] += len(conts)
-                        self.host_seconds["merge"] = self.host_seconds.get("merge", 0.0) + time.perf_counter() - tm
+                d_bytes, d_offsets, d_lens, d_raw, side = self._swap_side(pb, host_off, raw, B, d_bytes, d_offsets,
+                                                                          d_lens, d_raw)
                 copied = torch.cuda.Event()
                 copied.record()
-            if tl is not None:
-                tl["k0"] = torch.cuda.Event(enable_timing=True)
-                tl["k0"].record(sl.engine.stream)
+            self._tl_event("k0", sl.engine.stream)
             self._launch(sl, d_bytes, d_offsets, B, None, cfg=cfg, account=True, raw_mask=d_raw, sizes=sizes,
                          probe=pb.info, lengths=d_lens)
-            if tl is not None:
-                tl["k1"] = torch.cuda.Event(enable_timing=True)
-                tl["k1"].record(sl.engine.stream)
-                tl["t1"] = time.perf_counter()
-                tl["slot"] = self._slots.index(sl)
-                self._timeline.append(tl)
+            self._tl_done(sl)
             if buf_j is not None:
                 sl.buf_done[buf_j] = sl.event
             sl.inflight = (d_bytes, d_offsets, d_raw, d_lens, side)  # device copies live until the slot's next batch
-        except BaseException:
+            launched = True
+        finally:
+            # whatever the batch still holds goes back, launched or not: once the uploads were
+            # enqueued (``copied``) the owner waits for them, before that there is nothing to wait for
             if pb.staging is not None:
                 self._ring.release(pb.staging, copied)
             if pb.spans is not None:
                 self._source.retire(pb.spans, copied)
-            if pb.feed is not None:
+            if pb.feed is not None and not launched:  # never reached its copy (_upload_feed owns it from there)
                 self._source.release(pb.feed)
-            raise
-        if pb.staging is not None:
-            self._ring.release(pb.staging, copied)
-        if pb.spans is not None:
-            self._source.retire(pb.spans, copied)
         self.host_seconds["launch"] += time.perf_counter() - t0
         return sl
+
+    # ---- a batch's input into HBM, one routine per route.  Each runs on the slot's stream
+    # (``sl.engine.on_stream()``) and returns (d_bytes, d_offsets, d_lens, buf_j): ``d_lens`` only
+    # for the spans form, ``buf_j`` the slot's feed input buffer the batch reads (else None).
+    def _upload(self, sl: _Slot, pb: _Prepared, host_buf, host_off, nbytes: int, B: int):
+        if pb.dev is not None:
+            return self._upload_ahead(pb)
+        if pb.feed is not None:
+            return self._upload_feed(sl, pb, B)
+        if pb.spans is not None:
+            return self._upload_spans(sl, pb, host_off, B)
+        return self._upload_packed(host_buf, host_off, nbytes)
+
+    def _upload_ahead(self, pb: _Prepared):
+        """Copied to HBM when it joined the side look-ahead (``_stage_on_device``): wait for that copy."""
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(pb.copied)
+        d_bytes, d_offsets, d_lens = pb.dev
+        for t in pb.dev:
+            if t is not None:
+                t.record_stream(cur)
+        return d_bytes, d_offsets, d_lens, None
+
+    def _upload_feed(self, sl: _Slot, pb: _Prepared, B: int):
+        """The native feed's pinned slot: bytes + offsets in two DMAs (``dino_feed_copy``) on the
+        copy stream, into the one of the slot's two input buffers its previous batch did not
+        read.  From here the feed batch is this routine's: released if the copy fails, else the
+        feed takes its slot back when the copy retires."""
+        fb, pb.feed = pb.feed, None
+        j = sl.buf_next
+        sl.buf_next ^= 1
+        if sl.d_ins[j] is None or sl.d_ins[j].numel() < fb.nbytes + 64:
+            if sl.buf_done[j] is not None:  # the old buffer's last reader must finish first
+                sl.buf_done[j].synchronize()
+            sl.d_ins[j] = torch.empty(max(fb.nbytes, 1) * 9 // 8 + 64, dtype=torch.uint8, device=self.device)
+        if sl.d_offs[j] is None or sl.d_offs[j].numel() < B + 1:
+            if sl.buf_done[j] is not None:
+                sl.buf_done[j].synchronize()
+            sl.d_offs[j] = torch.empty(B + 1, dtype=torch.int64, device=self.device)
+        cs = self._copy_stream if self._copy_stream is not None else sl.engine.stream
+        try:
+            if cs is not sl.engine.stream and sl.buf_done[j] is not None:
+                cs.wait_event(sl.buf_done[j])
+            self._tl_event("c0", cs, stamp="issue")
+            self._source.copy(fb, sl.d_ins[j].data_ptr(), sl.d_offs[j].data_ptr(),
+                              cs.cuda_stream if cs is not None else 0)
+            self._tl_event("c1", cs)
+        except BaseException:
+            self._source.release(fb)
+            raise
+        if cs is not sl.engine.stream:
+            arrived = torch.cuda.Event()
+            arrived.record(cs)
+            torch.cuda.current_stream(self.device).wait_event(arrived)
+        return sl.d_ins[j], sl.d_offs[j][: B + 1], None, j
+
+    def _upload_spans(self, sl: _Slot, pb: _Prepared, host_off: torch.Tensor, B: int):
+        """DMA the batch's page-locked shard ranges as they lie (no host copy)."""
+        nbytes = int(pb.spans.offsets[-1])
+        if sl.d_in is None or sl.d_in.numel() < nbytes:
+            sl.d_in = torch.empty(max(nbytes, 1) * 9 // 8 + 64, dtype=torch.uint8, device=self.device)
+        pos = 0
+        for addr, n in pb.spans.parts:
+            sl.engine.copy_from_host(sl.d_in, pos, addr, n)
+            pos += n
+        d_lens = pb.staging.lens[:B].to(self.device, non_blocking=True)
+        return sl.d_in, host_off.to(self.device, non_blocking=True), d_lens, None
+
+    def _upload_packed(self, host_buf: torch.Tensor, host_off: torch.Tensor, nbytes: int):
+        """The batch packed in its pinned staging: the bytes, then the offsets."""
+        d_bytes = host_buf[:max(nbytes, 1)].to(self.device, non_blocking=True)
+        return d_bytes, host_off.to(self.device, non_blocking=True), None, None
+
+    def _swap_side(self, pb: _Prepared, host_off, raw, B: int, d_bytes, d_offsets, d_lens, d_raw):
+        """After the upload: the batch's input with its coefficient-buffer images that were decoded
+        ahead (progside.py) swapped for their device containers.  Returns (d_bytes, d_offsets,
+        d_lens, d_raw, the containers); the input as it came and None when there are none."""
+        if pb.side is None:
+            return d_bytes, d_offsets, d_lens, d_raw, None
+        if pb.side.pending:  # still in the side pool: decode it now
+            self._side.flush()
+        conts = pb.side.ready()
+        if not conts:
+            return d_bytes, d_offsets, d_lens, d_raw, None
+        tm = time.perf_counter()
+        base = host_off.numpy() if host_off is not None else pb.offsets
+        # image lengths: the spans form's own (its offsets point into shard
+        # ranges, the gaps hold tar headers and sidecars); packed: the gaps
+        base_lens = pb.spans.lens if pb.spans is not None else \
+            pb.lens if pb.lens is not None else np.diff(base[: B + 1])
+        d_bytes, d_offsets, d_lens, d_raw = self._merge_side(pb.side, conts, d_bytes, int(base[B]), base, base_lens,
+                                                             raw, B)
+        self.stats["side_decoded"] += len(conts)
+        self.host_seconds["merge"] = self.host_seconds.get("merge", 0.0) + time.perf_counter() - tm
+        return d_bytes, d_offsets, d_lens, d_raw, conts
 
     def _merge_side(self, job, conts: dict, d_bytes: torch.Tensor, nbytes: int, base_off: np.ndarray,
                     base_lens: np.ndarray, raw: torch.Tensor | None, B: int):
@@ -1274,26 +951,23 @@ class MI355XAugPipeline:
             for i, c in conts.items():
                 off[i], lens[i], rawm[i] = c.data_ptr() - base, int(c.numel()), 1
             off[B] = cap
-            h_off = torch.from_numpy(off).pin_memory()
-            h_len = torch.from_numpy(lens.astype(np.int64)).pin_memory()
-            h_raw = torch.from_numpy(rawm).pin_memory()
-            return (d_bytes, h_off.to(self.device, non_blocking=True), h_len.to(self.device, non_blocking=True),
-                    h_raw.to(self.device, non_blocking=True))
-        pos = (nbytes + 15) & ~15
-        total = pos + sum((int(c.numel()) + 15) & ~15 for c in conts.values())
-        merged = torch.empty(total + 64, dtype=torch.uint8, device=self.device)
-        merged[:nbytes].copy_(d_bytes[:nbytes], non_blocking=True)
-        for i, c in conts.items():
-            n = int(c.numel())
-            merged[pos:pos + n].copy_(c, non_blocking=True)
-            c.record_stream(cur)
-            off[i], lens[i], rawm[i] = pos, n, 1
-            pos += (n + 15) & ~15
-        off[B] = total
+        else:  # the batch's bytes, then the containers, in a buffer of their own
+            pos = (nbytes + 15) & ~15
+            total = pos + sum((int(c.numel()) + 15) & ~15 for c in conts.values())
+            merged = torch.empty(total + 64, dtype=torch.uint8, device=self.device)
+            merged[:nbytes].copy_(d_bytes[:nbytes], non_blocking=True)
+            for i, c in conts.items():
+                n = int(c.numel())
+                merged[pos:pos + n].copy_(c, non_blocking=True)
+                c.record_stream(cur)
+                off[i], lens[i], rawm[i] = pos, n, 1
+                pos += (n + 15) & ~15
+            off[B] = total
+            d_bytes = merged
         h_off = torch.from_numpy(off).pin_memory()
         h_len = torch.from_numpy(lens.astype(np.int64)).pin_memory()
         h_raw = torch.from_numpy(rawm).pin_memory()
-        return (merged, h_off.to(self.device, non_blocking=True), h_len.to(self.device, non_blocking=True),
+        return (d_bytes, h_off.to(self.device, non_blocking=True), h_len.to(self.device, non_blocking=True),
                 h_raw.to(self.device, non_blocking=True))
 
     def _refresh(self, sl: _Slot, sizes: tuple[int, int]) -> None:
@@ -1461,148 +1135,3 @@ class MI355XPipelineIterator:
         self._source_done = False
         self._queue.clear()  # batches prepared but not launched are the source's next ones: kept
         self._pipe.restart_epoch()
-
-
-def resize_scratch_bound(w: int, h: int, ow: int, oh: int) -> int:
-    """Augment-workspace bytes that hold a decoded w x h image's decode-only scratch at
-    ow x oh: an upper bound of csrc/plan.hpp ``dec_scratch(...).total`` (its tap counts are
-    two below these or less, and 64 covers its three 16-byte roundings)."""
-    kh = 2 * (-(-2 * w // ow)) + 3
-    kv = 2 * (-(-2 * h // oh)) + 3
-    return ow * (2 + kh) * 4 + oh * (2 + kv) * 4 + h * ow * 3 + 64
-
-
-class MI355XUserAugPipeline:
-    """``UserAugSpec`` on the GPU: the reference's ``CPUUserAugPipeline.run_one_batch``
-    (cpu.py:484-500) — decode, resize the shorter side to ``decode_size`` (Pillow BICUBIC,
-    torchvision ``Resize`` geometry), normalise — as HIP kernels (``dino_resize_batch``),
-    then ``aug_fn`` on the device tensor.  Like the reference (which ``torch.stack``s the
-    per-image tensors) every image of a batch must resize to the same shape; an
-    undecodable image contributes zeros of shape (3, decode_size, decode_size)."""
-
-    def __init__(self, source: Any, spec, batch_size: int, out_dtype="bf16", device: int = 0,
-                 max_image_dim: int = 0, workspace_bytes: int = 0, norm=None, resample_filter=None):
-        self._source = source
-        self._spec = spec
-        self._batch_size = int(batch_size)
-        self._out = _out_code(out_dtype)
-        self._norm = norm
-        self._max_image_dim = int(max_image_dim)
-        self._engine = IngestEngine(device, max_batch=self._batch_size, max_views=1, max_crop_size=8,
-                                    max_image_dim=max_image_dim, workspace_bytes=workspace_bytes)
-        if resample_filter is not None:  # Pillow filter of the resize (None: bicubic)
-            self._engine.set_resample_filter(resample_filter)
-        self.stats = {"batches": 0, "images": 0, "status": Counter(), "host_decoded": 0}
-        self._pending_status: deque = deque()
-        self._closed = False
-
-    @property
-    def device(self) -> torch.device:
-        return self._engine.device
-
-    def _fold_status(self, st: np.ndarray) -> None:
-        self.stats["batches"] += 1
-        self.stats["images"] += len(st)
-        self.stats["status"].update(int(x) for x in st)
-        if (st > 0).any():
-            warnings.warn(f"MI355XUserAugPipeline: {int((st > 0).sum())} decodable image(s) returned zeros",
-                          RuntimeWarning, stacklevel=3)
-
-    def _drain_status(self, block: bool = False) -> None:
-        while self._pending_status and (block or self._pending_status[0][1].query()):
-            host, ev = self._pending_status.popleft()
-            ev.synchronize()
-            self._fold_status(host[:, 0].numpy())
-
-    def flush_stats(self) -> dict:
-        self._drain_status(block=True)
-        return self.stats
-
-    def run_one_batch(self) -> dict[str, torch.Tensor]:
-        if self._closed:
-            raise RuntimeError("MI355XUserAugPipeline.run_one_batch() called after close()")
-        from .config import resize_shorter_size
-        jpegs = self._source()
-        assert len(jpegs) == self._batch_size
-        host_buf, offsets = pack_jpegs(jpegs, pin=True)
-        info, ws, _ = fallback.probe(host_buf.data_ptr(), offsets.numpy(), len(jpegs), self._max_image_dim)
-        raw = None
-        if np.isin(info[:, 0], (fallback.IMG_UNSUPPORTED, fallback.IMG_LIMIT)).any():
-            jpegs, n, rm = fallback.hand_over(list(jpegs), info[:, 0])
-            self.stats["host_decoded"] += n
-            host_buf, offsets = pack_jpegs(jpegs, pin=True)
-            info, ws, _ = fallback.probe(host_buf.data_ptr(), offsets.numpy(), len(jpegs), self._max_image_dim,
-                                         raw_mask=rm)
-            raw = torch.from_numpy(rm).pin_memory()
-        ds = int(self._spec.decode_size)
-        shapes = {resize_shorter_size(int(w), int(h), ds) if st == 0 else (ds, ds)
-                  for st, w, h, _ in info.tolist()}
-        if len(shapes) != 1:  # the reference's torch.stack raises on unequal shapes
-            raise RuntimeError(f"stack expects each tensor to be equal size, got resized shapes {sorted(shapes)}")
-        ow, oh = shapes.pop()
-        aws = sum(resize_scratch_bound(w, h, ow, oh) for st, w, h, _ in info.tolist() if st == 0)
-        self._engine.reserve(ws, aws)
-        eng = self._engine
-        d_bytes = host_buf.to(self.device, non_blocking=True)
-        d_off = offsets.to(self.device, non_blocking=True)
-        d_raw = raw.to(self.device, non_blocking=True) if raw is not None else None
-        if self._norm is not None:
-            self._norm_dev = torch.from_numpy(self._norm.batch_records(len(jpegs))).to(self.device)
-            eng.set_norm(self._norm_dev)
-        d_info = eng.decode(d_bytes, d_off, len(jpegs), raw_mask=d_raw)
-        out = eng.resize_batch(ow, oh, self._spec.mean, self._spec.std, self._out)
-        eng.batch_info(d_info)
-        self._inflight = (host_buf, d_bytes, d_off, d_raw)
-        probe_ok = info[:, 0] == 0
-        if (ow, oh) != (ds, ds) and probe_ok.any():
-            # an image that probes fine but fails on the device (damaged entropy data) is the
-            # reference's (ds, ds) zero tensor, which its torch.stack refuses next to (ow, oh):
-            # only then does the batch need its device status before returning
-            st = d_info[:, 0].cpu().numpy()
-            if ((st != 0) & probe_ok).any():
-                raise RuntimeError(f"stack expects each tensor to be equal size, got resized shapes "
-                                   f"{sorted({(ow, oh), (ds, ds)})}")
-            self._fold_status(st)
-        else:  # shapes cannot disagree: the status is read back asynchronously
-            host = torch.empty(d_info.shape, dtype=d_info.dtype, pin_memory=True)
-            host.copy_(d_info, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._pending_status.append((host, ev))
-            self._drain_status()
-        return self._spec.aug_fn(out)
-
-    def close(self) -> None:
-        if not self._closed:
-            self._closed = True
-            self._drain_status(block=True)
-            self._engine.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-
-class MI355XUserAugIterator:
-    """The DALIBackend's ``_UserAugIterator`` contract (dali_backend.py:27-56): ``next()`` ->
-    ``[aug_fn(decoded)]``, with a ValueError when a view of ``output_map`` is missing."""
-
-    def __init__(self, pipeline: MI355XUserAugPipeline, output_map: list[str]) -> None:
-        self._pipe = pipeline
-        self._map = list(output_map)
-
-    def __iter__(self):
-        return self
-
-    def __next__(self) -> list[dict[str, torch.Tensor]]:
-        augmented = self._pipe.run_one_batch()
-        missing = [k for k in self._map if k not in augmented]
-        if missing:
-            raise ValueError(f"UserAugSpec.aug_fn did not return expected view(s): {missing}. "
-                             f"Got keys: {list(augmented.keys())}")
-        return [augmented]
-
-    def reset(self) -> None:
-        """Stateless between batches."""

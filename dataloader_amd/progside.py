@@ -33,6 +33,7 @@ import torch
 
 from . import _lib, fallback
 from .engine import IngestEngine
+from .streams import role_stream
 from .tario import gather
 
 
@@ -128,7 +129,6 @@ class _SideEngine:
     def __init__(self, device: torch.device, max_images: int, max_image_dim: int, cu_count: int = 0,
                  dedicated: bool = True, index: int = 0, stream_set: int = 0, lanes: bool = False,
                  four_component: bool = False):
-        from .pipeline import role_stream
         self.raw = _create_stream(device.index or 0, int(cu_count)) if dedicated else None
         self.stream = self.raw if dedicated else role_stream(device, "side", index, stream_set)
         self.eng = IngestEngine(device, max_batch=max_images, max_views=1, max_crop_size=8,
@@ -214,7 +214,7 @@ class DeviceSideDecoder:
         self.min_images = max(1, min(int(min_images), self.max_images))
         self.cap = max(1, int(engines))
         self.max_image_dim = int(max_image_dim)
-        self.stream_set = int(stream_set)  # the owning pipeline's role streams (pipeline.acquire_stream_set)
+        self.stream_set = int(stream_set)  # the owning pipeline's role streams (streams.acquire_stream_set)
         self.lanes = bool(lanes)           # the side contexts' decoder (side_plan)
         self.four_component = bool(four_component)  # the side contexts decode CMYK / YCCK files
         self.lane_min = int(os.environ.get("DINO_SIDE_LANE_MIN", LANE_MIN_POOL))  # smaller pools: wave decoder

@@ -46,7 +46,9 @@ def test_launcher_gives_each_worker_its_rank(capfd):
     assert len({d["MASTER_PORT"] for d in lines}) == 1
 
 
-def test_launcher_refuses_too_few_devices():
+def test_launcher_refuses_too_few_devices(monkeypatch):
+    for v in bench._VIS_VARS:  # a job that runs under per-rank device isolation is let through: not this case
+        monkeypatch.delenv(v, raising=False)
     with pytest.raises(SystemExit, match="only 1 GPU"):
         bench.launch_ranks(8, [], devices=1)
     with pytest.raises(SystemExit, match="no GPU"):
