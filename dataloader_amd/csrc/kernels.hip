@@ -3569,8 +3569,9 @@ __device__ __forceinline__ void final_compute(const uint8_t* __restrict__ tile, 
 // (the parity tests hold blurred views to one level on <= 0.5 % of pixels, as for the
 // 2-D form against torch's conv2d); per output it takes 2 KS (KS + kBlurStrip - 1) /
 // kBlurStrip fmas instead of KS^2.  k_final (the large views' bands) takes it: 0.378 ->
-// 0.358 ms per C2 step; k_vfinal keeps the 2-D form, whose registers leave it 7 waves per
-// SIMD instead of 5 (0.466 vs 0.494 ms).
+// 0.358 ms per C2 step.  k_vfinal takes the same two passes through an LDS float strip
+// (vfinal_blur_lds, same fma order, so the same bits): this register form cost it
+// occupancy (82 VGPRs, 5 waves per SIMD instead of 7: 0.494 vs 0.466 ms for the 2-D form).
 constexpr int kBlurStrip = 4;
 template <int KS, typename OutT>
 __device__ __forceinline__ void final_compute_sep(const uint8_t* __restrict__ tile, int tp, int64_t tplane, int nr,
@@ -3749,6 +3750,91 @@ __host__ __device__ __forceinline__ int vfinal_tile_bytes(int S) {
 constexpr int kVFinalMaxS = 128;  // views up to this size take the fused kernel
 constexpr int kVFinalThreads = 512;  // 8 waves per view: the vertical pass is load-latency bound
 
+// The separable blur's float strip: one channel's row-pass results for a chunk of
+// vfinal_chunk_rows(S) output rows and their 2 pad halo rows (pad <= 4 for the separable
+// sizes).  12 KiB is 24 + 8 rows at S = 96 and 16 + 8 at S = 128; with it the kernel's LDS
+// (51.4 KB at S = 96, bf16) still lets three workgroups share a CU's 160 KB, as many as
+// its registers allow.  The 2-D weights of the other kernel sizes lie in the same bytes.
+constexpr int kVfStripBytes = 12 * 1024;
+constexpr int kVfSepPad = 4;
+__host__ __device__ __forceinline__ int vfinal_chunk_rows(int S) {
+  const int r = kVfStripBytes / (4 * ((S + 3) & ~3)) - 2 * kVfSepPad;
+  return r < S ? r : S;
+}
+// LDS of k_vfinal: k1[16] | tile | ntab[3][256] | strip (or k2[256])
+template <typename OutT>
+__host__ __device__ __forceinline__ int vfinal_strip_off(int S) {
+  return (16 * (int)sizeof(float) + vfinal_tile_bytes(S) + 3 * 256 * (int)sizeof(OutT) + 15) & ~15;
+}
+
+// Blur (KS 3..9) + solarize + normalise + cast of a whole view held in k_vfinal's tile, in
+// the fma order of final_compute_sep (so the bits of k_final's separable form), with the
+// row pass's results in LDS instead of registers.  Per channel and chunk of rows: a lane
+// convolves 4 adjacent columns of one tile row with the 1-D kernel and writes 4 floats to
+// the strip; after a barrier a lane convolves its 4 columns of KS strip rows with the 1-D
+// kernel again and finishes one output row (two rows per lane would halve the strip reads
+// but take 91 VGPRs, one workgroup per CU fewer).
+template <int KS, typename OutT>
+__device__ __forceinline__ void vfinal_blur_lds(const uint8_t* __restrict__ tile, int tp, int64_t tplane,
+                                                float* __restrict__ strip, int S, const float* __restrict__ k1,
+                                                bool solarize, const OutT* __restrict__ ntab, OutT* __restrict__ out) {
+  constexpr int PAD = KS / 2, NW = (KS + 3 + 3) / 4;
+  static_assert(PAD <= kVfSepPad, "the strip holds 2 kVfSepPad halo rows");
+  float w[KS];
+#pragma unroll
+  for (int k = 0; k < KS; ++k) w[k] = k1[k];
+  const int nq = (S + 3) >> 2, sp = 4 * nq;  // strip pitch in floats
+  const int rows = vfinal_chunk_rows(S);
+  const int64_t N = (int64_t)S * S;
+  const bool vec_ok = (S & 3) == 0;
+  const FastDiv dq((uint32_t)nq);
+  for (int ch = 0; ch < 3; ++ch) {
+    const uint8_t* pl = tile + ch * tplane;
+    const OutT* tb = ntab + 256 * ch;
+    for (int c0 = 0; c0 < S; c0 += rows) {
+      const int nr = min(rows, S - c0), tr = nr + 2 * PAD;
+      for (int e = threadIdx.x; e < tr * nq; e += blockDim.x) {
+        const int lr = (int)dq.div((uint32_t)e), q = e - lr * nq;
+        const uint32_t* row = (const uint32_t*)(pl + (c0 + lr) * tp) + q;
+        uint32_t wv[NW];
+#pragma unroll
+        for (int k = 0; k < NW; ++k) wv[k] = row[k];
+        float h[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int c = 0; c < KS; ++c)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int bi = c + j;
+            h[j] = fmaf(w[c], (float)((wv[bi >> 2] >> (8 * (bi & 3))) & 255u), h[j]);
+          }
+        *(float4*)(strip + lr * sp + 4 * q) = make_float4(h[0], h[1], h[2], h[3]);
+      }
+      __syncthreads();
+      for (int e = threadIdx.x; e < nr * nq; e += blockDim.x) {
+        const int y = (int)dq.div((uint32_t)e), x0 = 4 * (e - y * nq);
+        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int a = 0; a < KS; ++a) {
+          const float4 hv = *(const float4*)(strip + (y + a) * sp + x0);
+          acc[0] = fmaf(w[a], hv.x, acc[0]);
+          acc[1] = fmaf(w[a], hv.y, acc[1]);
+          acc[2] = fmaf(w[a], hv.z, acc[2]);
+          acc[3] = fmaf(w[a], hv.w, acc[3]);
+        }
+        OutT o4[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float rr = rintf(acc[j]);
+          const int v = rr <= 0.0f ? 0 : (rr >= 255.0f ? 255 : (int)rr);
+          o4[j] = tb[solarize ? solarize_u8(v) : v];
+        }
+        store_vals4<OutT>(out, ch * N + (int64_t)(c0 + y) * S + x0, o4, min(4, S - x0), vec_ok);
+      }
+      __syncthreads();  // the next chunk's row pass writes the strip again
+    }
+  }
+}
+
 template <typename OutT>
 __global__ void __launch_bounds__(kVFinalThreads) k_vfinal(const ImgDesc* __restrict__ desc, const dino_view_params* __restrict__ prm,
                                                 const ViewPlan* __restrict__ plan, int nv, int v0, const uint8_t* __restrict__ ws,
@@ -3757,8 +3843,10 @@ __global__ void __launch_bounds__(kVFinalThreads) k_vfinal(const ImgDesc* __rest
   const BlkIdx bk = xcd_blk();
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   __shared__ uint32_t s_part[kVFinalThreads / 64];
-  FinalLds& H = *reinterpret_cast<FinalLds*>(smem);
-  uint8_t* tile = smem + sizeof(FinalLds);
+  float* k1 = reinterpret_cast<float*>(smem);
+  uint8_t* tile = smem + 16 * sizeof(float);
+  float* strip = reinterpret_cast<float*>(smem + vfinal_strip_off<OutT>(S));
+  float* k2 = strip;  // (the generic kernel sizes' 2-D weights: those views use no strip)
   const int b = bk.y, v = v0 + bk.x;
   const int i = b * nv + v;
   const ViewPlan vp = plan[i];
@@ -3779,7 +3867,7 @@ __global__ void __launch_bounds__(kVFinalThreads) k_vfinal(const ImgDesc* __rest
   const int tp = final_tile_pitch(S, pad);
   const int64_t tplane = (int64_t)(S + 2 * pad) * tp;
   OutT* ntab = reinterpret_cast<OutT*>(tile + vfinal_tile_bytes(S));
-  if (p.blur && threadIdx.x == 0) gaussian_kernel1d(ks, p.sigma, H.k1);
+  if (p.blur && threadIdx.x == 0) gaussian_kernel1d(ks, p.sigma, k1);
   for (int e = threadIdx.x; e < 3 * 256; e += blockDim.x) {
     const int c = e >> 8;
     ntab[e] = out_cast<OutT>(u8_normalize(e & 255, nb ? nb[c] : cfg.mean[c], nb ? nb[3 + c] : cfg.std[c]));
@@ -3851,16 +3939,18 @@ __global__ void __launch_bounds__(kVFinalThreads) k_vfinal(const ImgDesc* __rest
     }
   }
   __syncthreads();
-  if (p.blur && threadIdx.x < ks * ks) H.k2[threadIdx.x] = H.k1[threadIdx.x / ks] * H.k1[threadIdx.x % ks];
-  __syncthreads();
   const bool sol = p.solarize != 0;
   switch (ks) {
-    case 1: final_compute<1, OutT>(tile, tp, tplane, S, 0, S, ks, H.k2, sol, ntab, out); break;
-    case 3: final_compute<3, OutT>(tile, tp, tplane, S, 0, S, ks, H.k2, sol, ntab, out); break;
-    case 5: final_compute<5, OutT>(tile, tp, tplane, S, 0, S, ks, H.k2, sol, ntab, out); break;
-    case 7: final_compute<7, OutT>(tile, tp, tplane, S, 0, S, ks, H.k2, sol, ntab, out); break;
-    case 9: final_compute<9, OutT>(tile, tp, tplane, S, 0, S, ks, H.k2, sol, ntab, out); break;
-    default: final_compute<0, OutT>(tile, tp, tplane, S, 0, S, ks, H.k2, sol, ntab, out); break;
+    case 1: final_compute<1, OutT>(tile, tp, tplane, S, 0, S, ks, k2, sol, ntab, out); break;
+    case 3: vfinal_blur_lds<3, OutT>(tile, tp, tplane, strip, S, k1, sol, ntab, out); break;
+    case 5: vfinal_blur_lds<5, OutT>(tile, tp, tplane, strip, S, k1, sol, ntab, out); break;
+    case 7: vfinal_blur_lds<7, OutT>(tile, tp, tplane, strip, S, k1, sol, ntab, out); break;
+    case 9: vfinal_blur_lds<9, OutT>(tile, tp, tplane, strip, S, k1, sol, ntab, out); break;
+    default:  // other sizes: the 2-D form
+      if (threadIdx.x < ks * ks) k2[threadIdx.x] = k1[threadIdx.x / ks] * k1[threadIdx.x % ks];
+      __syncthreads();
+      final_compute<0, OutT>(tile, tp, tplane, S, 0, S, ks, k2, sol, ntab, out);
+      break;
   }
 }
 
@@ -4193,6 +4283,19 @@ hipError_t init_launch_geom(int device, LaunchGeom* g) {
                                kHresizeLds)) != hipSuccess)
     return e;
   g->grid_hr = persistent_grid(reinterpret_cast<const void*>(&k_hresize), kHresizeLds, cus);
+  // k_vfinal's tile and strip pass 64 KiB above S = 100
+  const int vf_lds = vfinal_strip_off<float>(kVFinalMaxS) + kVfStripBytes;
+  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vfinal<uint16_t>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               vf_lds)) != hipSuccess ||
+      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vfinal<float>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               vf_lds)) != hipSuccess ||
+      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vfinal<uint8_t>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               vf_lds)) != hipSuccess)
+    return e;
+  // views up to this size take k_vfinal, larger ones k_vert + k_final (DINO_VFINAL_MAX_S: 0 sends
+  // every view through the two kernels, for parity tests and A/B runs)
+  const char* vm = getenv("DINO_VFINAL_MAX_S");
+  g->vfinal_max_s = vm ? min(max(atoi(vm), 0), kVFinalMaxS) : kVFinalMaxS;
   if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_plscan), hipFuncAttributeMaxDynamicSharedMemorySize,
                                kPLscanLds)) != hipSuccess)
     return e;
@@ -4264,8 +4367,8 @@ static hipError_t launch_augment_class(const AugmentArgs& a, int v0, int nvc, in
   TIMED(tm, kKRcoeffs, s, (k_rcoeffs<<<dim3(nvc, B), rc_threads, 0, s>>>(a.desc, a.params, a.plan, nv, v0, a.filter, a.ws, a.aws)));
   TIMED(tm, kKHresize, s,
         (k_hresize<<<a.grid_hr, 256, kHresizeLds, s>>>(a.desc, a.params, a.plan, nv, v0, nvc, B, a.ws, a.aws)));
-  if (S <= kVFinalMaxS) {  // small views: vertical pass and epilogue fused, the view stays in LDS
-    const int lds = (int)sizeof(FinalLds) + vfinal_tile_bytes(S) + 3 * 256 * (int)sizeof(OutT);
+  if (S <= a.vfinal_max_s) {  // small views: vertical pass and epilogue fused, the view stays in LDS
+    const int lds = vfinal_strip_off<OutT>(S) + kVfStripBytes;
     TIMED(tm, kfin, s,
           (k_vfinal<OutT><<<dim3(nvc, B), kVFinalThreads, lds, s>>>(a.desc, a.params, a.plan, nv, v0, a.ws, a.aws, a.views, a.cfg,
                                                          S, a.norm)));

@@ -62,6 +62,7 @@ struct LaunchGeom {
   int32_t prog_lane; // 1: eligible progressive images take k_plscan (DINO_PROG_LANE=0: all k_pscan)
   int32_t scan_prio; // 1: scan waves at the batch kernels' issue priority (DINO_SCAN_PRIO)
   int32_t grid_hr;   // persistent k_hresize grid (occupancy x CUs)
+  int32_t vfinal_max_s;  // views up to this size take the fused k_vfinal (DINO_VFINAL_MAX_S, at most 128)
 };
 
 // Coefficient-buffer images of a batch (k_plan zeroes, k_pwalk registers, k_pscan
@@ -113,6 +114,7 @@ struct AugmentArgs {
   const float* norm;       // per-image {mean[3], std[3]} ([0, 1] scale), nullable -> cfg.mean / cfg.std
   int32_t grid_hr;         // LaunchGeom::grid_hr
   int32_t filter;          // ResampleFilter of every view's resample (0: BICUBIC)
+  int32_t vfinal_max_s;    // LaunchGeom::vfinal_max_s
 };
 
 // Decode-only recipe (dino_resize_batch).
