@@ -21,6 +21,15 @@ inline void probe_one(const uint8_t* p, int64_t len, bool raw, int32_t max_image
     // a probe has no context: a four-component frame is parsed as a context with
     // dino_ctx_set_four_component on would, and reported below as kind 3
     parse_jpeg(p, len, max_image_dim, &d, raw, true);
+    // a table that a scan uses and libjpeg rejects (JERR_BAD_HUFF_TABLE) fails the image in
+    // k_htab / k_pwalk: the same check here, so that the status is the decode's
+    HuffDerived tab;
+    if (d.status == DINO_IMG_OK && d.kind == 0) {
+      for (int c = 0; c < d.ncomp; ++c)
+        if (!huff_build_derived(p + d.huff_off[d.comp[c].td], true, &tab) ||
+            !huff_build_derived(p + d.huff_off[4 + d.comp[c].ta], false, &tab))
+          d.status = DINO_IMG_CORRUPT;
+    }
     if (d.status == DINO_IMG_OK && d.kind == 1) {
       HostMarkerFinder find;
       if (prog_walk(p, len, &d, scans, find) == DINO_IMG_OK) {
@@ -28,7 +37,10 @@ inline void probe_one(const uint8_t* p, int64_t len, bool raw, int32_t max_image
         int32_t slot_off[kPMaxTabs];
         uint8_t slot_dc[kPMaxTabs];
         uint64_t ts[kMaxScans];
-        if (prog_table_slots(scans, d.n_scans, slot_off, slot_dc, ts, kPMaxTabs) < 0) d.status = DINO_IMG_UNSUPPORTED;
+        const int ntab = prog_table_slots(scans, d.n_scans, slot_off, slot_dc, ts, kPMaxTabs);
+        if (ntab < 0) d.status = DINO_IMG_UNSUPPORTED;
+        for (int s = 0; s < ntab; ++s)
+          if (!huff_build_derived(p + slot_off[s], slot_dc[s] != 0, &tab)) d.status = DINO_IMG_CORRUPT;
       }
     }
   }

@@ -65,9 +65,10 @@ def adobe_segment(transform: int | None, short: bool = False) -> bytes:
 
 
 def encode4(img: np.ndarray, scans: list[dict], samp=S11, quality: int = 90, progressive: bool = False, restart=0,
-            adobe: int | None = 0, adobe_short: bool = False, jfif: bool = False, comp_ids=(1, 2, 3, 4)) -> bytes:
+            adobe: int | None = 0, adobe_short: bool = False, jfif: bool = False, comp_ids=(1, 2, 3, 4), table_hook=None) -> bytes:
     """A four-component JPEG of the planes ``img`` (H x W x 4, stored as they are: what they mean is
-    the decoder's business) with an explicit scan script (``jpeg_writer.scan``)."""
+    the decoder's business) with an explicit scan script (``jpeg_writer.scan``); ``table_hook`` as
+    in ``jpeg_writer.encode``."""
     H, W, _ = img.shape
     mh, mv = max(s[0] for s in samp), max(s[1] for s in samp)
     mx, my = -(-W // (8 * mh)), -(-H // (8 * mv))
@@ -106,7 +107,8 @@ def encode4(img: np.ndarray, scans: list[dict], samp=S11, quality: int = 90, pro
         for slot in sorted(counter.freq):
             kind, k = slot
             slot_ids[slot] = k
-            bits, vals = jw.optimal_table(counter.freq[slot])
+            bits, vals = (jw.optimal_table(counter.freq[slot]) if table_hook is None
+                          else table_hook(kind, k, counter.freq[slot]))
             dht += bytes([(0 if kind == "dc" else 16) | k]) + bytes(bits) + bytes(vals)
             tables[slot] = jw.canonical_codes(bits, vals)
         if dht:

@@ -160,14 +160,26 @@ class _ScanCoder:
     """Codes one scan twice: a counting pass (symbol statistics -> optimal tables) and an
     emitting pass with those tables.  Symbols go to table slots ('dc', k) / ('ac', k)."""
 
-    def __init__(self, emit: bool, tables=None):
+    def __init__(self, emit: bool, tables=None, bad_code_every: int = 0):
         self.emit = emit
         self.tables = tables or {}
         self.freq: dict = {}
         self.w = BitWriter()
+        # every n-th symbol 0 (a DC category 0 or an AC EOB of a sequential scan) goes out as
+        # 17 one-bits: no table assigns the all-ones prefix, so no code of <= 16 bits matches
+        # and libjpeg reads a zero after 17 bits (jdhuff.c JWRN_HUFF_BAD_CODE)
+        self.bad_code_every = bad_code_every
+        self.zeros = 0
+        self.bad_codes = 0
 
     def sym(self, slot, s: int):
         if self.emit:
+            if s == 0 and self.bad_code_every:
+                self.zeros += 1
+                if self.zeros % self.bad_code_every == 0:
+                    self.bad_codes += 1
+                    self.w.bits((1 << 17) - 1, 17)
+                    return
             code, ln = self.tables[slot][s]
             self.w.bits(code, ln)
         else:
@@ -348,7 +360,8 @@ def _rgb_to_ycc(rgb: np.ndarray) -> np.ndarray:
 
 def encode(img: np.ndarray, scans: list[dict], quality: int = 85, samp=((2, 2), (1, 1), (1, 1)),
            progressive: bool = False, restart=None, comp_ids=(1, 2, 3), jfif: bool = True,
-           before_scan: dict | None = None, coef_hook=None) -> bytes:
+           before_scan: dict | None = None, coef_hook=None, table_hook=None, share_tables: bool = False,
+           table_ids=None, bad_code_every: int = 0, report: dict | None = None) -> bytes:
     """Encode ``img`` (H x W x 3 RGB or H x W gray) with an explicit scan script.
 
     scans: [{"comps": (frame component indices in scan order), "ss", "se", "ah", "al"}];
@@ -359,7 +372,14 @@ def encode(img: np.ndarray, scans: list[dict], quality: int = 85, samp=((2, 2), 
     ``coef_hook(coefs, qts) -> (coefs, qts)``: replaces the quantized coefficients
     ([bh, bw, 64] natural order per component) and quantization tables (<= 255) before
     coding, for tests that need chosen coefficient values.
+    ``table_hook(kind, slot_index, freq) -> (bits16, vals)`` stands in for ``optimal_table``
+    (kind "dc" / "ac"; freq: the 256 symbol counts of the table's slots).  ``table_ids``: the
+    table id of scan component k (both classes; default k % 4); slots given the same id, or all
+    of them under ``share_tables``, share one table built from their summed frequencies.
+    ``bad_code_every`` = n (sequential files): every n-th symbol 0 is written as 17 one-bits;
+    ``report["bad_codes"]`` receives their number.
     """
+    assert not (bad_code_every and progressive)
     gray = img.ndim == 2
     planes_full = [img.astype(np.float64)] if gray else list(np.moveaxis(_rgb_to_ycc(img), -1, 0))
     nc = len(planes_full)
@@ -409,17 +429,27 @@ def encode(img: np.ndarray, scans: list[dict], quality: int = 85, samp=((2, 2), 
         _code_scan(frame, coefs, scan, counter, ri)
         tables, dht = {}, bytearray()
         slot_ids = {}
-        for slot in sorted(counter.freq, key=lambda s: (s[0], s[1])):
+        slots = sorted(counter.freq, key=lambda s: (s[0], s[1]))
+        for slot in slots:
             kind, k = slot
-            tid = k % 4
-            slot_ids[slot] = tid
-            bits, vals = optimal_table(counter.freq[slot])
+            slot_ids[slot] = 0 if share_tables else table_ids[k] if table_ids is not None else k % 4
+        for slot in slots:
+            kind, k = slot
+            tid = slot_ids[slot]
+            group = [s for s in slots if s[0] == kind and slot_ids[s] == tid]
+            if slot != group[0]:  # one table per (class, id): written with its first slot
+                tables[slot] = tables[group[0]]
+                continue
+            freq = counter.freq[slot] if len(group) == 1 else [sum(f) for f in zip(*(counter.freq[s] for s in group))]
+            bits, vals = optimal_table(freq) if table_hook is None else table_hook(kind, k, freq)
             dht += bytes([(0 if kind == "dc" else 16) | tid]) + bytes(bits) + bytes(vals)
             tables[slot] = canonical_codes(bits, vals)
         if dht:
             out += _seg(0xC4, bytes(dht))
-        emitter = _ScanCoder(True, tables)
+        emitter = _ScanCoder(True, tables, bad_code_every)
         segs = _code_scan(frame, coefs, scan, emitter, ri)
+        if report is not None:
+            report["bad_codes"] = report.get("bad_codes", 0) + emitter.bad_codes
         comps = scan["comps"]
         sos = bytes([len(comps)])
         for k, c in enumerate(comps):
