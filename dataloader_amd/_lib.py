@@ -95,6 +95,7 @@ def load() -> ctypes.CDLL:
         "dino_ctx_set_prog_decoder": (i32, [vp, i32]),
         "dino_ctx_set_resample_filter": (i32, [vp, i32]),
         "dino_ctx_set_four_component": (i32, [vp, i32]),
+        "dino_ctx_set_png": (i32, [vp, i32]),
         "dino_resample_coeffs_host": (i32, [i32, i32, i32, i32, i32, vp, vp, vp]),
         "dino_kernel_times": (i32, [vp, vp, vp, i32]),
         "dino_tar_index": (i32, [vp, i64, vp, i64, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
@@ -137,4 +138,4 @@ def exported_symbols() -> list[str]:
             "dino_feed_set_shard_wait", "dino_feed_set_shuffle", "dino_feed_set_epoch",
             "dino_feed_next", "dino_feed_copy", "dino_feed_release", "dino_feed_reset", "dino_feed_stats",
             "dino_feed_last_error", "dino_stream_create", "dino_stream_destroy",
-            "dino_ctx_set_resample_filter", "dino_resample_coeffs_host", "dino_ctx_set_four_component"]
+            "dino_ctx_set_resample_filter", "dino_resample_coeffs_host", "dino_ctx_set_four_component", "dino_ctx_set_png"]

@@ -122,7 +122,7 @@ class MI355XBackend:
     def __init__(self, max_image_dim: int = 0, workspace_bytes: int = 0, max_in_flight: int = 3,
                  hbm_fraction: float = 0.15, host_workers: int | None = None, multiscan_route: str = "side",
                  side_ahead: int | None = None, resample_filter: str | None = None,
-                 four_component: str = "host") -> None:
+                 four_component: str = "host", png: str = "off") -> None:
         # Pillow filter of every resize: None = bicubic everywhere (CPUBackend parity, which
         # ignores EvalAugSpec.interpolation too); a filter's name applies to every recipe;
         # "spec" honours EvalAugSpec.interpolation as the reference's GPU peer does
@@ -139,6 +139,13 @@ class MI355XBackend:
         if four_component not in ("host", "device"):
             raise ValueError(f"four_component must be 'host' or 'device', not {four_component!r}")
         self._four_component = four_component
+        # PNG files: "off" (default) leaves them zero-filled as every file that is not a JPEG,
+        # "host" hands them to Pillow, "device" decodes the common forms (8 bits, no interlace)
+        # in the HIP kernels and hands the rest to Pillow.  The UserAugSpec pipeline hands every PNG over
+        # under "host" and "device" alike
+        if png not in ("off", "host", "device"):
+            raise ValueError(f"png must be 'off', 'host' or 'device', not {png!r}")
+        self._png = png
         self._max_image_dim = max_image_dim
         self._workspace_bytes = workspace_bytes
         self._max_in_flight = max(1, int(max_in_flight))
@@ -248,7 +255,7 @@ class MI355XBackend:
             return MI355XUserAugPipeline(source, aug_spec, getattr(source, "_batch_size", 1),
                                          out_dtype=pipeline_cfg.output_dtype, device=pipeline_cfg.device_id,
                                          max_image_dim=self._max_image_dim, workspace_bytes=self._workspace_bytes,
-                                         norm=norm, resample_filter=self.spec_filter(aug_spec))
+                                         norm=norm, resample_filter=self.spec_filter(aug_spec), png=self._png)
         if _is_dinov2_spec(aug_spec):
             aug_cfg = aug_spec.aug_cfg
             names = None
@@ -292,6 +299,7 @@ class MI355XBackend:
             side_ahead=self.side_look_ahead(pipeline_cfg, source, depth),
             resample_filter=self.spec_filter(aug_spec),
             four_component=self._four_component,
+            png=self._png,
         )
 
     def build_pipeline_iterator(self, pipeline: Any, aug_spec: Any, output_map: list[str],

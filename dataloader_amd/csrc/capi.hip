@@ -64,6 +64,7 @@ struct dino_ctx {
   LaunchGeom geom{};
   int32_t filter = kBicubic;  // dino_ctx_set_resample_filter: read at each augment / resize launch
   int32_t four_component = 0; // dino_ctx_set_four_component: read at each decode launch
+  int32_t png = 0;            // dino_ctx_set_png: read at each decode launch
   KernelTimer* timer = nullptr;
   KernelTimer* tm() { return timer && timer->enabled ? timer : nullptr; }
 };
@@ -148,7 +149,7 @@ int dino_decode_spans(dino_ctx* c, const uint8_t* d_bytes, const int64_t* d_offs
     return fail(DINO_EINVAL, "dino_decode: batch %s%lld exceeds ctx max_batch", "", batch);
   hipStream_t s = (hipStream_t)stream;
   DecodeArgs a{d_bytes, d_offsets, d_lengths, d_raw_mask, batch, c->lim.max_image_dim, c->d_desc, c->d_ws,
-               c->ws_size, c->geom, c->d_pctl, c->four_component};
+               c->ws_size, c->geom, c->d_pctl, c->four_component, c->png};
   hipError_t e = launch_decode(a, s, c->tm());
   if (e != hipSuccess) return hip_fail(e, "dino_decode");
   if (d_info && (e = launch_info(c->d_desc, batch, d_info, s)) != hipSuccess) return hip_fail(e, "dino_decode(info)");
@@ -323,7 +324,10 @@ int dino_augment_need(const int32_t* info, int32_t batch, const dino_aug_config*
   int64_t aws = 0;
   for (int32_t i = 0; i < batch; ++i) {
     // (kind 3: a four-component image, which a context with the option on decodes)
-    if (info[4 * i] != DINO_IMG_OK && !(info[4 * i] == DINO_IMG_UNSUPPORTED && info[4 * i + 3] == 3)) continue;
+    // (kind 4: a PNG, which a context with dino_ctx_set_png on decodes)
+    if (info[4 * i] != DINO_IMG_OK && !(info[4 * i] == DINO_IMG_UNSUPPORTED && info[4 * i + 3] == 3) &&
+        !(info[4 * i] == DINO_IMG_CORRUPT && info[4 * i + 3] == 4))
+      continue;
     for (int v = 0; v < cfg->n_global + cfg->n_local; ++v)
       aws += view_scratch_bound(v < cfg->n_global ? cfg->global_size : cfg->local_size, info[4 * i + 1],
                                 info[4 * i + 2]);
@@ -556,6 +560,12 @@ int dino_ctx_set_four_component(dino_ctx* c, int32_t on) {
   return DINO_OK;
 }
 
+int dino_ctx_set_png(dino_ctx* c, int32_t on) {
+  if (!c) return fail(DINO_EINVAL, "dino_ctx_set_png: null ctx%s%lld");
+  c->png = on != 0;  // read at each launch (launch_decode)
+  return DINO_OK;
+}
+
 int dino_ctx_set_resample_filter(dino_ctx* c, int32_t filter) {
   if (!c) return fail(DINO_EINVAL, "dino_ctx_set_resample_filter: null ctx%s%lld");
   if (filter < 0 || filter >= kNumResampleFilters)
@@ -647,9 +657,17 @@ int dino_debug_region(dino_ctx* c, int32_t index, int32_t region, void* d_dst, i
       src = c->d_ws + d.rst_off;
       n = d.kind == 0 ? 4 * (int64_t)std::min(d.n_rst, d.n_rst_max + 1) : 0;
       break;
+    case 10:  // kind 4: the IDAT payloads joined into one zlib stream (k_pngwalk)
+      src = c->d_ws + d.ent_off;
+      n = d.kind == 4 ? d.ent_len : 0;
+      break;
+    case 11:  // kind 4: the inflated, still-filtered rows (k_inflate)
+      src = c->d_ws + d.plane_off;
+      n = d.kind == 4 ? (int64_t)d.height * (1 + (int64_t)d.width * d.max_h) : 0;
+      break;
     default: return fail(DINO_EINVAL, "dino_debug_region: region %s%lld", "", region);
   }
-  if (d.status != 0 && region != 0) return fail(DINO_EINVAL, "dino_debug_region: image status %s%lld", "", d.status);
+  if (d.status != 0 && region != 0 && !(d.kind == 4 && (region == 10 || region == 11) && d.status < 0)) return fail(DINO_EINVAL, "dino_debug_region: image status %s%lld", "", d.status);
   if (n > max_bytes) n = max_bytes;
   e = hipMemcpyAsync(d_dst, src, n, hipMemcpyDeviceToDevice, s);
   return e == hipSuccess ? (int)0 : hip_fail(e, "dino_debug_region");

@@ -33,7 +33,7 @@ struct ViewPlan {
 enum KernelId : int {
   kKParse = 0, kKPlan, kKDestuff, kKHuff1, kKIdct, kKColor, kKParams, kKVplan, kKRcoeffs, kKHresize,
   kKFinalGlobal, kKFinalLocal, kKVertGlobal, kKVertLocal, kKDcscan, kKHtab, kKHseg, kKHuff2, kKHuff3, kKProg,
-  kKPwalk, kKPlscan, kKPapply, kKNumKernels
+  kKPwalk, kKPlscan, kKPapply, kKPng, kKNumKernels
 };
 
 struct KernelTimer {
@@ -63,6 +63,7 @@ struct LaunchGeom {
   int32_t scan_prio; // 1: scan waves at the batch kernels' issue priority (DINO_SCAN_PRIO)
   int32_t grid_hr;   // persistent k_hresize grid (occupancy x CUs)
   int32_t vfinal_max_s;  // views up to this size take the fused k_vfinal (DINO_VFINAL_MAX_S, at most 128)
+  int32_t grid_inf;  // persistent k_inflate grid (one-wave workgroups; contexts with dino_ctx_set_png on)
 };
 
 // Coefficient-buffer images of a batch (k_plan zeroes, k_pwalk registers, k_pscan
@@ -72,7 +73,7 @@ struct LaunchGeom {
 // lticket t = scan t / ngroups of the 64-image group t % ngroups.
 struct PCtl {
   uint32_t ticket, nprog, max_scans, cap;
-  uint32_t lticket, nlane, lmax_scans, pad;
+  uint32_t lticket, nlane, lmax_scans, pad;  // pad: k_inflate's ticket counter (k_pngwalk zeroes it)
   int32_t pimg[1];  // [max_batch]
 };
 DHD int64_t pctl_bytes(int max_batch) { return 32 + 4 * (int64_t)(max_batch > 0 ? max_batch : 1); }
@@ -91,6 +92,7 @@ struct DecodeArgs {
   LaunchGeom geom;
   PCtl* pctl;
   int32_t four_component;   // 1: four-component frames decode (dino_ctx_set_four_component), 0: DINO_IMG_UNSUPPORTED
+  int32_t png;              // 1: PNG files decode (dino_ctx_set_png), 0: DINO_IMG_CORRUPT as any non-JPEG
 };
 
 // Output pointers travel as a kernel argument (no host->device copy whose source

@@ -5,6 +5,7 @@
 
 #include "kernels.hpp"
 #include "progressive.hpp"
+#include "png_parse.hpp"
 #include "pscan.hpp"
 #include "lscan.hpp"
 #include "resize.hpp"
@@ -81,11 +82,21 @@ DHD DsRole ds_part_role(int part, int lead, int n, int E, int ds_items) {
   return {k0 < E, E < n ? (E >= k0 && E < k1) : part == ds_items - 1};
 }
 
+// kPng: the caller may hold PNG images (kind 4).  k_plan of a context without dino_ctx_set_png is
+// instantiated without them and stays the code it was.
+template <bool kPng = true>
 DHD ChunkSizes image_chunk_bytes(const ImgDesc& d) {
   ChunkSizes z{};
   if (d.status != DINO_IMG_OK) return z;
   z.rgb = align16((int64_t)d.width * d.height * 3 + 16);
   if (d.kind == 2) return chunk_finish(z);
+  if (kPng && d.kind == kPngKind) {  // the joined zlib stream, one carried row, the filtered rows, the palette
+    z.ent = align16((int64_t)d.scan_len + 64);
+    z.coef = align16((int64_t)d.width * 4 + 16);
+    z.plane = align16(png_inflated_bytes(d) + 64);
+    z.htab = kPngPalBytes;
+    return chunk_finish(z);
+  }
   // the planes hold a byte per coefficient of the dense int16 layout coef_bytes counts
   // (jpeg_parse.hpp: 64 and 128 bytes a block of every component's bw x bh grid)
   z.plane = align16(d.coef_bytes / 2);

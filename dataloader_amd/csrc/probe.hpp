@@ -4,6 +4,7 @@
 
 #include "jpeg_parse.hpp"
 #include "plan.hpp"
+#include "png_parse.hpp"
 #include "progressive.hpp"
 
 namespace dino {
@@ -14,6 +15,33 @@ constexpr int32_t kMaxImageDim = 65535;
 inline void probe_one(const uint8_t* p, int64_t len, bool raw, int32_t max_image_dim, const dino_aug_config* cfg,
                ScanRec* scans, int32_t* info_row, int64_t* ws, int64_t* aws) {
   ImgDesc d;
+  // A file with the PNG signature keeps the status every context without dino_ctx_set_png gives
+  // it (DINO_IMG_CORRUPT); the kind says what a context with the option on does: 4, decodes it
+  // (its workspace and views are counted, as for kind 3), or 5, declines it (bit depths other
+  // than 8, Adam7, APNG, chunks the walk does not verify, a side above max_image_dim).  A PNG
+  // on which Pillow raises keeps kind -1.
+  if (len > 0 && !raw && png_signature(p, len)) {
+    d.kind = 0;
+    d.width = d.height = 0;
+    int st = parse_png_head(p, len, max_image_dim, &d);
+    PngWalk w;
+    if (st == DINO_IMG_OK) st = png_walk(p, len, d.color, &w);
+    const bool dev = st == DINO_IMG_OK, declined = st > 0;
+    if (info_row) {
+      info_row[0] = DINO_IMG_CORRUPT;
+      info_row[1] = dev ? d.width : 0;
+      info_row[2] = dev ? d.height : 0;
+      info_row[3] = dev ? kPngKind : (declined ? kPngKindDeclined : -1);
+    }
+    if (!dev) return;
+    d.status = DINO_IMG_OK;
+    *ws += image_chunk_bytes(d).total();
+    if (cfg) {
+      for (int v = 0; v < cfg->n_global + cfg->n_local; ++v)
+        *aws += view_scratch_bound(v < cfg->n_global ? cfg->global_size : cfg->local_size, d.width, d.height);
+    }
+    return;
+  }
   if (len <= 0) {
     d.status = DINO_IMG_CORRUPT;
     d.width = d.height = d.ncomp = 0;

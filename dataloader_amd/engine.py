@@ -77,6 +77,7 @@ class IngestEngine:
         self.prog_lanes: bool | None = None  # set_prog_decoder's choice (None: the library default)
         self.resample_filter = 0  # set_resample_filter's choice (DINO_FILTER_*; 0: bicubic)
         self.four_component = False  # set_four_component's choice (False: CMYK / YCCK files report status 1)
+        self.png = False  # set_png's choice (False: PNG files report status -1, as any non-JPEG)
 
     def _s(self) -> ctypes.c_void_p:
         return _stream_handle(self.device, self.stream)
@@ -133,7 +134,7 @@ class IngestEngine:
     KERNEL_NAMES = ["k_parse", "k_plan", "k_destuff", "k_huff1", "k_idct", "k_color", "k_params", "k_vplan",
                     "k_rcoeffs", "k_hresize", "k_final_global", "k_final_local", "k_vert_global", "k_vert_local",
                     "k_dcscan", "k_htab", "k_hseg", "k_huff2", "k_huff3", "k_prog", "k_pwalk", "k_plscan",
-                    "k_papply"]
+                    "k_papply", "k_png"]
 
     def set_prog_decoder(self, lanes: bool) -> None:
         """Decode this context's coefficient-buffer images with the lane decoder (``True``:
@@ -156,6 +157,13 @@ class IngestEngine:
         default) from the next call on (``dino_ctx_set_four_component``)."""
         _lib.check(self.lib.dino_ctx_set_four_component(self._ctx, int(bool(on))), "dino_ctx_set_four_component")
         self.four_component = bool(on)
+
+    def set_png(self, on: bool) -> None:
+        """Decode the common PNG forms (8 bits, colour types 0 / 2 / 3 / 4 / 6, no interlace) on
+        this context (``True``) to the RGB Pillow's ``convert("RGB")`` gives, or report every PNG
+        ``DINO_IMG_CORRUPT`` (``False``, the default) from the next call on (``dino_ctx_set_png``)."""
+        _lib.check(self.lib.dino_ctx_set_png(self._ctx, int(bool(on))), "dino_ctx_set_png")
+        self.png = bool(on)
 
     def set_timing(self, enable: bool) -> None:
         _lib.check(self.lib.dino_set_timing(self._ctx, int(enable)), "dino_set_timing")

@@ -40,6 +40,42 @@ IMG_LIMIT = 4
 KIND_MULTISCAN = 1
 KIND_FOUR_COMPONENT = 3  # dino_probe: status 1, decodable by a context with the four-component option on
 FOUR_COMPONENT_MODES = ("host", "device")
+IMG_CORRUPT = -1
+KIND_PNG = 4           # dino_probe: status -1, a PNG a context with dino_ctx_set_png on decodes
+KIND_PNG_DECLINED = 5  # dino_probe: status -1, a PNG such a context leaves to the caller
+PNG_MODES = ("off", "host", "device")
+
+
+def check_png(mode: str) -> None:
+    if mode not in PNG_MODES:
+        raise ValueError(f"png must be 'off', 'host' or 'device', not {mode!r}")
+
+
+def png_mask(info: np.ndarray, device: bool = True, declined: bool = True) -> np.ndarray:
+    """Rows of a probed batch that are PNG files (status -1): those a context with
+    ``dino_ctx_set_png`` on decodes (kind 4, ``device``) and those it declines (kind 5,
+    ``declined``).  A PNG on which Pillow raises is neither (kind -1)."""
+    kinds = ([KIND_PNG] if device else []) + ([KIND_PNG_DECLINED] if declined else [])
+    return (info[:, 0] == IMG_CORRUPT) & np.isin(info[:, 3], kinds)
+
+
+def accept_png(info: np.ndarray, png: str = "device") -> np.ndarray:
+    """The probe's info as a pipeline with the option ``png`` treats the batch.  ``"device"``:
+    kind-4 rows become status 0, kind 1 (decoded on contexts with ``dino_ctx_set_png`` on and
+    routed like any coefficient-buffer image: a PNG costs a progressive file's latency or
+    more), kind-5 rows status ``IMG_UNSUPPORTED`` (handed to Pillow).  ``"host"``: both become
+    ``IMG_UNSUPPORTED``.  ``"off"``: nothing changes (every PNG stays status -1: zeros).  A
+    copy; the probe's workspace numbers already count the kind-4 images."""
+    check_png(png)
+    out = np.array(info, np.int32, copy=True)
+    if png == "off":
+        return out
+    dev = png_mask(out, True, False)
+    out[png_mask(out, png == "host", True), 0] = IMG_UNSUPPORTED
+    if png == "device":
+        out[dev, 0] = 0
+        out[dev, 3] = KIND_MULTISCAN
+    return out
 
 
 def four_component_mask(info: np.ndarray) -> np.ndarray:
@@ -147,7 +183,7 @@ def pillow_container(jpeg) -> bytes:
 
 def hand_over(jpegs: list, status: np.ndarray, mask: np.ndarray | None = None,
               pool: "HostDecoder | None" = None, four_component: str = "host",
-              kind: np.ndarray | None = None) -> tuple[list, int, np.ndarray]:
+              kind: np.ndarray | None = None, png: str = "off") -> tuple[list, int, np.ndarray]:
     """Replace the images the GPU decoder does not decode (``status`` ``IMG_UNSUPPORTED`` or
     ``IMG_LIMIT``, or ``mask`` when given) by Pillow-decoded raw RGB containers (zero bytes
     where Pillow raises), in ``pool``'s worker processes when given.  With ``four_component``
@@ -155,8 +191,12 @@ def hand_over(jpegs: list, status: np.ndarray, mask: np.ndarray | None = None,
     (kind 3) stay as they are.  Returns (new list, images handed over, raw mask: uint8[B], 1
     where the new entry is a container — the mask dino_probe / dino_decode need to accept it)."""
     _check_four_component(four_component)
+    check_png(png)
     if mask is None:
         mask = np.isin(status, (IMG_UNSUPPORTED, IMG_LIMIT))
+        if png != "off" and kind is not None:  # PNGs (status -1): "host" both kinds, "device" the declined ones
+            mask |= png_mask(np.stack([np.asarray(status), np.zeros_like(status), np.zeros_like(status),
+                                       np.asarray(kind)], 1), png == "host", True)
         if four_component == "device" and kind is not None:
             mask &= ~((np.asarray(status) == IMG_UNSUPPORTED) & (np.asarray(kind) == KIND_FOUR_COMPONENT))
     idx = np.flatnonzero(mask)
@@ -184,9 +224,12 @@ def _check_four_component(mode: str) -> None:
 
 
 def route_mask(info: np.ndarray, host_fallback: bool, multiscan_route: str, host_max: int,
-               four_component: str = "host") -> np.ndarray:
+               four_component: str = "host", png: str = "off") -> np.ndarray:
     """Images of a probed batch to decode with Pillow on the host.
 
+    * with ``png`` ``"host"`` every PNG Pillow may decode (kinds 4 and 5) is handed over, with
+      ``"device"`` only those the device declines (kind 5), and the others count as
+      coefficient-buffer images below (``accept_png``); with ``"off"`` (default) none;
     * with ``four_component`` ``"device"`` (contexts with ``dino_ctx_set_four_component`` on),
       four-component files the device decodes (status 1, kind 3) count as coefficient-buffer
       images below, not as unsupported ones; with ``"host"`` (default) they are handed over;
@@ -200,6 +243,7 @@ def route_mask(info: np.ndarray, host_fallback: bool, multiscan_route: str, host
       ``host_max`` (the host decodes ~6 ms per 640x480 image per worker, off the
       critical path when prepared one batch ahead), else none."""
     _check_four_component(four_component)
+    info = accept_png(info, png)
     if four_component == "device":
         info = accept_four_component(info)
     mask = np.isin(info[:, 0], (IMG_UNSUPPORTED, IMG_LIMIT)) if host_fallback else np.zeros(len(info), bool)

@@ -128,8 +128,13 @@ class MI355XAugPipeline:
                  multiscan_route: str = "auto", host_workers: int | None = None,
                  multiscan_host_max: int | None = None, prefetch: int | None = None,
                  start_host_pool: bool = False, side_ahead: int = 64, resample_filter=None,
-                 four_component: str = "host"):
+                 four_component: str = "host", png: str = "off"):
         self._source = source
+        # PNG files: "off" leaves them status -1 (zeros), "host" hands them to Pillow, "device"
+        # decodes the common forms in the kernels (every slot and side context gets
+        # dino_ctx_set_png) and hands the rest to Pillow (fallback.accept_png)
+        fallback.check_png(png)
+        self._png = png
         self._aug_cfg = aug_cfg
         # four-component (CMYK / YCCK) JPEGs: "host" hands them to Pillow, "device" decodes them in
         # the kernels (every slot and side context gets dino_ctx_set_four_component) and routes them
@@ -169,7 +174,7 @@ class MI355XAugPipeline:
         # GPU decoder left to Pillow, and workspace regrowths
         # four_component: CMYK / YCCK images kept on the device (four_component="device")
         self.stats = {"batches": 0, "images": 0, "status": Counter(), "host_decoded": 0, "reserves": 0,
-                      "side_decoded": 0, "four_component": 0}
+                      "side_decoded": 0, "four_component": 0, "png_device": 0, "png_host": 0}
         # host-side seconds per phase: pull / pack / probe (host half), wait (launch thread
         # waiting for the host half), launch (H2D copies + kernel enqueue)
         self.host_seconds = {"pull": 0.0, "pack": 0.0, "probe": 0.0, "wait": 0.0, "launch": 0.0}
@@ -228,6 +233,8 @@ class MI355XAugPipeline:
                 eng.set_resample_filter(self._resample_filter)
             if self._four_component == "device":
                 eng.set_four_component(True)
+            if self._png == "device":
+                eng.set_png(True)
             self._slots.append(_Slot(eng))
         self._last: _Slot = self._slots[0]          # the last launched batch
         # output sets (shape key, tensors, consumer stream), batch n -> set n % (depth + 1)
@@ -400,6 +407,12 @@ class MI355XAugPipeline:
         """A probe's info as this pipeline's contexts decode the batch: with
         ``four_component="device"`` the four-component rows become decodable coefficient-buffer
         images (``fallback.accept_four_component``), counted in ``stats`` once per batch."""
+        if self._png != "off":  # (fallback.accept_png; PNGs kept on the device / handed to Pillow)
+            if count:
+                dev = int(fallback.png_mask(info, True, False).sum()) if self._png == "device" else 0
+                self.stats["png_device"] += dev
+                self.stats["png_host"] += int(fallback.png_mask(info).sum()) - dev
+            info = fallback.accept_png(info, self._png)
         if self._four_component != "device":
             return info
         if count:
@@ -548,7 +561,8 @@ class MI355XAugPipeline:
             lanes, pool = progside.side_plan(self._side_ahead)
             self._side = progside.DeviceSideDecoder(self.device, max_images=pool, max_image_dim=self._max_image_dim,
                                                     stream_set=self._stream_set, lanes=lanes,
-                                                    four_component=self._four_component == "device")
+                                                    four_component=self._four_component == "device",
+                                                    png=self._png == "device")
             self.stats["side_lanes"] = lanes
         if pb.jpegs is not None:
             imgs = {int(i): pb.jpegs[i] for i in idx}

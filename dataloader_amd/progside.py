@@ -128,7 +128,7 @@ class _SideEngine:
 
     def __init__(self, device: torch.device, max_images: int, max_image_dim: int, cu_count: int = 0,
                  dedicated: bool = True, index: int = 0, stream_set: int = 0, lanes: bool = False,
-                 four_component: bool = False):
+                 four_component: bool = False, png: bool = False):
         self.raw = _create_stream(device.index or 0, int(cu_count)) if dedicated else None
         self.stream = self.raw if dedicated else role_stream(device, "side", index, stream_set)
         self.eng = IngestEngine(device, max_batch=max_images, max_views=1, max_crop_size=8,
@@ -136,6 +136,8 @@ class _SideEngine:
         self.eng.set_prog_decoder(lanes)
         if four_component:  # CMYK / YCCK files join the pools (the lane decoder leaves them to the wave decoder)
             self.eng.set_four_component(True)
+        if png:  # PNG files join the pools too (the PNG kernels run the same under either progressive decoder)
+            self.eng.set_png(True)
         self.copy = role_stream(device, "side_copy", index, stream_set)  # this context's torch stream (allocations, copies)
         self.last: torch.cuda.Event | None = None   # the engine's workspace is free once this completes
         self.keep = None                             # host / device inputs of the mini-batch in flight
@@ -195,7 +197,7 @@ class DeviceSideDecoder:
 
     def __init__(self, device: torch.device, max_images: int = WAVE_POOL, min_images: int | None = None,
                  engines: int | None = None, max_image_dim: int = 0, stream_set: int = 0, lanes: bool = False,
-                 four_component: bool = False):
+                 four_component: bool = False, png: bool = False):
         import os
         # measured (scripts/route_study.py, 16 progressive per 256-image batch, dedicated queues,
         # look-ahead 64, profiles/r03_side_pools.jsonl): pools of 16 images on 2 contexts 11.2k img/s,
@@ -217,6 +219,7 @@ class DeviceSideDecoder:
         self.stream_set = int(stream_set)  # the owning pipeline's role streams (streams.acquire_stream_set)
         self.lanes = bool(lanes)           # the side contexts' decoder (side_plan)
         self.four_component = bool(four_component)  # the side contexts decode CMYK / YCCK files
+        self.png = bool(png)                        # and the PNG files the device takes
         self.lane_min = int(os.environ.get("DINO_SIDE_LANE_MIN", LANE_MIN_POOL))  # smaller pools: wave decoder
         self._engines: list[_SideEngine] = []
         self._rr = 0
@@ -263,7 +266,7 @@ class DeviceSideDecoder:
         if len(self._engines) < self.cap:
             e = _SideEngine(self.device, self.max_images, self.max_image_dim, self.cu_count, self.dedicated,
                             index=len(self._engines), stream_set=self.stream_set, lanes=self.lanes,
-                            four_component=self.four_component)
+                            four_component=self.four_component, png=self.png)
             self._engines.append(e)
             return e
         e = self._engines[self._rr % len(self._engines)]
@@ -318,6 +321,8 @@ class DeviceSideDecoder:
         info, ws, _ = fallback.probe(hb.data_ptr(), off.numpy(), len(items), self.max_image_dim)
         if self.four_component:
             info = fallback.accept_four_component(info)
+        if self.png:
+            info = fallback.accept_png(info, "device")
         t3 = time.perf_counter()
         ph["probe"] += t3 - t2
         eng.reserve(ws, 0)

@@ -33,8 +33,13 @@ class MI355XUserAugPipeline:
     undecodable image contributes zeros of shape (3, decode_size, decode_size)."""
 
     def __init__(self, source: Any, spec, batch_size: int, out_dtype="bf16", device: int = 0,
-                 max_image_dim: int = 0, workspace_bytes: int = 0, norm=None, resample_filter=None):
+                 max_image_dim: int = 0, workspace_bytes: int = 0, norm=None, resample_filter=None,
+                 png: str = "off"):
         self._source = source
+        # PNG files: "off" leaves them zero-filled; "host" and "device" both hand every PNG Pillow may
+        # decode over to it (this pipeline's context does not decode them), as four-component files are
+        fallback.check_png(png)
+        self._png = png
         self._spec = spec
         self._batch_size = int(batch_size)
         self._out = _out_code(out_dtype)
@@ -79,8 +84,10 @@ class MI355XUserAugPipeline:
         host_buf, offsets = pack_jpegs(jpegs, pin=True)
         info, ws, _ = fallback.probe(host_buf.data_ptr(), offsets.numpy(), len(jpegs), self._max_image_dim)
         raw = None
-        if np.isin(info[:, 0], (fallback.IMG_UNSUPPORTED, fallback.IMG_LIMIT)).any():
-            jpegs, n, rm = fallback.hand_over(list(jpegs), info[:, 0])
+        png = "off" if self._png == "off" else "host"
+        if np.isin(info[:, 0], (fallback.IMG_UNSUPPORTED, fallback.IMG_LIMIT)).any() or \
+                (png != "off" and fallback.png_mask(info).any()):
+            jpegs, n, rm = fallback.hand_over(list(jpegs), info[:, 0], kind=info[:, 3], png=png)
             self.stats["host_decoded"] += n
             host_buf, offsets = pack_jpegs(jpegs, pin=True)
             info, ws, _ = fallback.probe(host_buf.data_ptr(), offsets.numpy(), len(jpegs), self._max_image_dim,

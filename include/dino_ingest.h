@@ -48,7 +48,9 @@
  *    buffer in one launch).  Still additive within ABI 4: dino_ctx_set_resample_filter
  *    (Pillow's BILINEAR / BOX / HAMMING / LANCZOS per context; BICUBIC stays the default)
  *    and dino_resample_coeffs_host; dino_ctx_set_four_component (four-component Adobe CMYK /
- *    YCCK JPEGs decoded on the device, off by default) and kind 3 in the probes' info.
+ *    YCCK JPEGs decoded on the device, off by default) and kind 3 in the probes' info;
+ *    dino_ctx_set_png (PNG files decoded on the device, off by default), kinds 4 and 5 in the
+ *    probes' info, dino_kernel_times id 23, dino_debug_region 10 and 11.
  */
 #ifndef DINO_INGEST_H
 #define DINO_INGEST_H
@@ -354,6 +356,21 @@ int dino_ctx_set_resample_filter(dino_ctx* ctx, int32_t filter);
  * path (kind 1), a baseline file of one interleaved scan included, so it costs a progressive
  * file's latency.  No reference counterpart: Pillow decodes them on a CPU thread (cpu.py:251). */
 int dino_ctx_set_four_component(dino_ctx* ctx, int32_t on);
+
+/* PNG files on this ctx, from the next call on: 0 (default) reports a PNG DINO_IMG_CORRUPT, as
+ * any file that is not a JPEG; non-zero decodes the common forms on the device to the RGB of
+ * Pillow's Image.open(..).convert("RGB"), bit for bit: 8 bits per sample, colour types 0, 2, 3,
+ * 4 and 6, no interlace, only the ancillary chunks whose handling the chunk walk verifies (gray
+ * replicated, alpha dropped, palette looked up; tRNS, gAMA, sRGB change no pixel).  A file with
+ * the PNG signature on which Pillow raises (a bad CRC before the first IDAT, a file that ends
+ * before it, a damaged stream) stays negative; every other one is then DINO_IMG_UNSUPPORTED, for
+ * the caller to decode.  The
+ * probes have no ctx: they keep DINO_IMG_CORRUPT for a PNG and report kind 4 (such a ctx
+ * decodes it; width, height, workspace and views are counted) or kind 5 (it declines it).
+ * What follows the last byte of the last row in the zlib stream (the rest of the final block,
+ * the Adler-32) is not examined.  dino_kernel_times id 23 ("k_png") sums the four PNG
+ * kernels; dino_debug_region 10 is the joined zlib stream, 11 the inflated, still-filtered rows. */
+int dino_ctx_set_png(dino_ctx* ctx, int32_t on);
 
 /* The coefficient code of the resample kernels run on the host (no GPU involved; tests and
  * introspection): for in_size -> out_size with `filter`, *ksize = taps reserved per output;
