@@ -44,6 +44,68 @@ DHD int check_dims(ImgDesc* d, int max_dim) {
   return d->status;
 }
 
+DHD uint32_t rd32be(const uint8_t* p) {
+  return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
+}
+
+// libjpeg next_marker() (jdmarker.c): from pos, skip garbage up to an FF, then fill FFs; an FF00
+// pair is garbage too (Pillow's loop skips it as "extraneous data (escaped 0xFF)").  Returns
+// the marker code and sets *after to the byte after it, or -1 at the end of the data.
+DHD int next_marker_at(const uint8_t* p, int64_t len, int64_t pos, int64_t* after) {
+  for (;;) {
+    while (pos < len && p[pos] != 0xFF) ++pos;
+    if (pos >= len) return -1;
+    while (pos < len && p[pos] == 0xFF) ++pos;
+    if (pos >= len) return -1;
+    const int c = p[pos++];
+    if (c != 0) {
+      *after = pos;
+      return c;
+    }
+  }
+}
+
+// Markers that read_markers (jdmarker.c) has no case for end the decode wherever they stand:
+// RES (02..BF), DHP, EXP and JPGn fall to its default (JERR_UNKNOWN_MARKER), JPG shares the
+// case of the unsupported SOFs (JERR_SOF_UNSUPPORTED).
+DHD bool marker_unknown_to_libjpeg(int m) {
+  return (m >= 0x02 && m < 0xC0) || m == 0xC8 || m == 0xDE || m == 0xDF || (m >= 0xF0 && m <= 0xFD);
+}
+// Segments both walks only skip: APPn, COM (skip_variable / get_interesting_appn; Pillow's APP
+// and COM handlers) and DNL (skip_variable; Pillow's Skip).  A length field below 2 costs its
+// two bytes and nothing else: libjpeg skips only `if (length > 0)` after `length -= 2`, and
+// Pillow's _safe_read returns b"" for a size <= 0.
+DHD bool marker_skipped(int m) { return (m >= 0xE0 && m <= 0xEF) || m == 0xFE || m == 0xDC; }
+
+// Pillow's APP handler walks the image resource blocks of an APP13 "Photoshop 3.0" segment
+// (JpegImagePlugin.APP) and catches struct.error only: a block that ends right after its
+// two-byte resource code leaves an IndexError at the name length (`s[offset]`), Image.open
+// raises and the reference zero-fills.  s[0..n): the payload.  True: Pillow raises.
+DHD bool photoshop_raises(const uint8_t* s, int n) {
+  if (n < 14 || s[13] != 0) return false;
+  const char* id = "Photoshop 3.0";
+  for (int k = 0; k < 13; ++k)
+    if (s[k] != (uint8_t)id[k]) return false;
+  int64_t o = 14;
+  while (o + 4 <= n && s[o] == '8' && s[o + 1] == 'B' && s[o + 2] == 'I' && s[o + 3] == 'M') {
+    o += 4;
+    if (o + 2 > n) return false;  // i16(s, offset): struct.error, caught
+    const int code = rd16(s + o);
+    o += 2;
+    if (o >= n) return true;      // name_len = s[offset]: IndexError
+    o += 1 + s[o];
+    o += o & 1;
+    if (o + 4 > n) return false;  // i32(s, offset): struct.error
+    const int64_t size = rd32be(s + o);
+    o += 4;
+    // ResolutionInfo reads 14 bytes of the (clipped) data: struct.error on fewer
+    if (code == 0x03ED && (o + size < n ? size : n - o) < 14) return false;
+    o += size;
+    o += o & 1;
+  }
+  return false;
+}
+
 // allow_raw: the caller marked this image as a pre-decoded RGB container (raw mask of
 // dino_decode / dino_probe).  The container's magic is never trusted in user data: an
 // unmarked file that starts with it is parsed as what it is (not a JPEG -> corrupt, as
@@ -89,18 +151,32 @@ DHD int parse_jpeg(const uint8_t* p, int64_t len, int max_dim, ImgDesc* d, bool 
 
   bool saw_sof = false, saw_jfif = false, saw_adobe = false;
   int adobe_transform = 0;
+  // Pillow's SOF handler sorts the APP2 "ICC_PROFILE\0" payloads seen so far and reads byte 13
+  // of the first (`self.icclist[0][13]`): an IndexError, so Image.open raises, when that one is
+  // shorter than 14 bytes.  All share their first 12 bytes, so the first is a 12-byte payload
+  // if there is one, else the 13-byte payload with the smallest sequence byte unless a longer
+  // payload has a smaller one (an equal one sorts after its 13-byte prefix).
+  bool icc12 = false;
+  int icc13_min = 256, icc_long_min = 256;
   int64_t pos = 2;
   for (;;) {
-    // next_marker(): skip garbage up to 0xFF, then any fill 0xFFs
-    while (pos < len && p[pos] != 0xFF) ++pos;
-    while (pos < len && p[pos] == 0xFF) ++pos;
-    if (pos >= len) return d->status;  // no SOS: Pillow raises
-    int m = p[pos++];
-    if (m == 0xD8 || m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;  // standalone markers
-    if (m == 0xD9) return d->status;                                    // EOI before SOS
+    int64_t after;
+    int m = next_marker_at(p, len, pos, &after);
+    if (m < 0) return d->status;  // no SOS: Pillow raises
+    pos = after;
+    if (m >= 0xD0 && m <= 0xD7) continue;  // RSTn: parameterless for both walks
+    // TEM is parameterless for libjpeg, but Pillow's loop (JpegImagePlugin._open) has no FF01
+    // in its MARKER table: "no marker found".  A second SOI: get_soi JERR_SOI_DUPLICATE.
+    if (m == 0x01 || m == 0xD8) return d->status;
+    if (m == 0xD9) return d->status;  // EOI before SOS
+    if (marker_unknown_to_libjpeg(m)) return d->status;
     if (pos + 2 > len) return d->status;
     int seglen = rd16(p + pos);
-    if (seglen < 2 || pos + seglen > len) return d->status;
+    if (seglen < 2) {
+      if (!marker_skipped(m)) return d->status;  // get_dqt / get_dht / get_dri / get_sof / get_sos: JERR_BAD_LENGTH
+      seglen = 2;
+    }
+    if (pos + seglen > len) return d->status;
     const uint8_t* s = p + pos + 2;
     int n = seglen - 2;
     switch (m) {
@@ -108,13 +184,15 @@ DHD int parse_jpeg(const uint8_t* p, int64_t len, int max_dim, ImgDesc* d, bool 
       case 0xC1:
       case 0xC2: {  // SOF0 baseline / SOF1 extended sequential / SOF2 progressive, Huffman
         if (saw_sof || n < 6) return (d->status = DINO_IMG_CORRUPT);
+        if (icc12 || (icc13_min < 256 && icc13_min <= icc_long_min)) return (d->status = DINO_IMG_CORRUPT);
         saw_sof = true;
         d->progressive = m == 0xC2;
         int prec = s[0];
         d->height = rd16(s + 1);
         d->width = rd16(s + 3);
         int nf = s[5];
-        if (n < 6 + 3 * nf || nf <= 0) return (d->status = DINO_IMG_CORRUPT);
+        // get_sof: `if (length != (cinfo->num_components * 3)) ERREXIT(JERR_BAD_LENGTH)`
+        if (n != 6 + 3 * nf || nf <= 0) return (d->status = DINO_IMG_CORRUPT);
         // Pillow's SOF handler raises for precision != 8 and for layer counts other than
         // 1, 3, 4 (JpegImagePlugin.SOF): the reference zero-fills those
         if (prec != 8) return (d->status = DINO_IMG_CORRUPT);
@@ -159,7 +237,9 @@ DHD int parse_jpeg(const uint8_t* p, int64_t len, int max_dim, ImgDesc* d, bool 
         int q = 0;
         while (q < n) {
           int pq = s[q] >> 4, tq = s[q] & 15;
-          if (tq > 3 || pq > 1) return (d->status = DINO_IMG_CORRUPT);
+          // get_dqt: `prec = n >> 4 ... if (prec) 16-bit`; Pillow's DQT: `1 if v // 16 == 0 else 2`
+          // bytes: any non-zero precision nibble is a 16-bit table
+          if (tq > 3) return (d->status = DINO_IMG_CORRUPT);
           int need = pq ? 128 : 64;
           if (q + 1 + need > n) return (d->status = DINO_IMG_CORRUPT);
           for (int k = 0; k < 64; ++k) {
@@ -171,8 +251,8 @@ DHD int parse_jpeg(const uint8_t* p, int64_t len, int max_dim, ImgDesc* d, bool 
         }
         break;
       }
-      case 0xDD:  // DRI
-        if (n < 2) return (d->status = DINO_IMG_CORRUPT);
+      case 0xDD:  // DRI (get_dri: `if (length != 4) ERREXIT(JERR_BAD_LENGTH)`)
+        if (n != 2) return (d->status = DINO_IMG_CORRUPT);
         d->restart_interval = rd16(s);
         break;
       case 0xE0:  // APP0: JFIF?
@@ -183,6 +263,21 @@ DHD int parse_jpeg(const uint8_t* p, int64_t len, int max_dim, ImgDesc* d, bool 
           // jdmarker.c examine_app0: JFIF only with the whole 14-byte header (APP0_DATA_LEN)
           if (n >= 14 && s[4] == 0) saw_jfif = true;
         }
+        break;
+      case 0xE2:  // APP2: ICC profile chunks before the frame header (see icc12 above)
+        if (!saw_sof && n >= 12) {
+          const char* id = "ICC_PROFILE";
+          bool is_icc = s[11] == 0;
+          for (int k = 0; k < 11; ++k) is_icc = is_icc && s[k] == (uint8_t)id[k];
+          if (is_icc) {
+            if (n == 12) icc12 = true;
+            else if (n == 13) icc13_min = s[12] < icc13_min ? s[12] : icc13_min;
+            else icc_long_min = s[12] < icc_long_min ? s[12] : icc_long_min;
+          }
+        }
+        break;
+      case 0xED:  // APP13: Photoshop image resources
+        if (photoshop_raises(s, n)) return (d->status = DINO_IMG_CORRUPT);
         break;
       case 0xEE:  // APP14: Adobe transform flag
         if (n >= 5 && s[0] == 'A' && s[1] == 'd' && s[2] == 'o' && s[3] == 'b' && s[4] == 'e') {
@@ -196,7 +291,8 @@ DHD int parse_jpeg(const uint8_t* p, int64_t len, int max_dim, ImgDesc* d, bool 
       case 0xDA: {  // SOS
         if (!saw_sof || n < 1) return (d->status = DINO_IMG_CORRUPT);
         int ns = s[0];
-        if (n < 4 + 2 * ns || ns < 1 || ns > 4) return (d->status = DINO_IMG_CORRUPT);
+        // get_sos: `if (length != (n * 2 + 6) || n < 1 || n > MAX_COMPS_IN_SCAN) ERREXIT(JERR_BAD_LENGTH)`
+        if (n != 4 + 2 * ns || ns < 1 || ns > 4) return (d->status = DINO_IMG_CORRUPT);
         // One interleaved scan of every component in frame order decodes on the
         // baseline path; anything else (progressive, components spread over several
         // scans, another component order) on the coefficient-buffer path (k_prog),
@@ -230,7 +326,7 @@ DHD int parse_jpeg(const uint8_t* p, int64_t len, int max_dim, ImgDesc* d, bool 
         goto have_scan;
       }
       default:
-        break;  // APPn, COM, other: skipped
+        break;  // APPn, COM, DNL: skipped
     }
     pos += seglen;
   }

@@ -28,9 +28,7 @@ constexpr int kPngKindDeclined = 5;  // the probes' kind of a PNG it leaves to P
 constexpr int kPngDecline = DINO_IMG_UNSUPPORTED;
 constexpr int kPngPalBytes = 1024;   // the image's palette area: 256 RGB entries (zero-filled), padded
 
-DHD uint32_t rd32be(const uint8_t* p) {
-  return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
-}
+// (rd32be: jpeg_parse.hpp)
 DHD bool png_signature(const uint8_t* p, int64_t len) {
   return len >= 8 && p[0] == 0x89 && p[1] == 'P' && p[2] == 'N' && p[3] == 'G' && p[4] == 0x0D && p[5] == 0x0A &&
          p[6] == 0x1A && p[7] == 0x0A;

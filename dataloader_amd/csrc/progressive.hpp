@@ -91,22 +91,7 @@ struct HostMarkerFinder {  // (memchr: the probe walks every scan of a progressi
   }
 };
 
-// libjpeg next_marker(): from pos, skip garbage up to an FF, then fill FFs; an FF00
-// pair is garbage too.  Returns the marker code and sets *after to the byte after it,
-// or -1 at the end of the data.
-DHD int next_marker_at(const uint8_t* p, int64_t len, int64_t pos, int64_t* after) {
-  for (;;) {
-    while (pos < len && p[pos] != 0xFF) ++pos;
-    if (pos >= len) return -1;
-    while (pos < len && p[pos] == 0xFF) ++pos;
-    if (pos >= len) return -1;
-    const int c = p[pos++];
-    if (c != 0) {
-      *after = pos;
-      return c;
-    }
-  }
-}
+// next_marker_at (libjpeg next_marker()) is in jpeg_parse.hpp.
 
 // The last coefficient (zigzag index) a scan may write.  On a corrupt stream an AC first
 // scan's run moves k up to se + 15 before the store and an AC refinement puts a new
@@ -153,9 +138,14 @@ DHD int prog_walk(const uint8_t* p, int64_t len, ImgDesc* d, ScanRec* scans, Fin
       pos = after;
       continue;
     }
+    if (marker_unknown_to_libjpeg(m)) return (d->status = DINO_IMG_CORRUPT);
     if (pos + 2 > len) return (d->status = DINO_IMG_TRUNCATED);
-    const int seglen = rd16(p + pos);
-    if (seglen < 2 || pos + seglen > len) return (d->status = seglen < 2 ? DINO_IMG_CORRUPT : DINO_IMG_TRUNCATED);
+    int seglen = rd16(p + pos);
+    if (seglen < 2) {  // APPn, COM, DNL: the two length bytes and nothing else (marker_skipped)
+      if (!marker_skipped(m)) return (d->status = DINO_IMG_CORRUPT);
+      seglen = 2;
+    }
+    if (pos + seglen > len) return (d->status = DINO_IMG_TRUNCATED);
     const uint8_t* s = p + pos + 2;
     const int sn = seglen - 2;
     int64_t next_pos = pos + seglen;
@@ -290,8 +280,8 @@ DHD int prog_walk(const uint8_t* p, int64_t len, ImgDesc* d, ScanRec* scans, Fin
         int q = 0;
         while (q < sn) {
           const int pq = s[q] >> 4, tq = s[q] & 15;
-          if (tq > 3 || pq > 1) return (d->status = DINO_IMG_CORRUPT);
-          const int need = pq ? 128 : 64;
+          if (tq > 3) return (d->status = DINO_IMG_CORRUPT);
+          const int need = pq ? 128 : 64;  // (get_dqt: any non-zero precision nibble is 16-bit)
           if (q + 1 + need > sn) return (d->status = DINO_IMG_CORRUPT);
           qt_redefined[tq] = true;
           q += 1 + need;
