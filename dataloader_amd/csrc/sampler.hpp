@@ -5,6 +5,15 @@
 // reference (process-global RNGs consumed by up to 16 threads in arbitrary
 // order) the result is independent of scheduling, and the drawn
 // record is exported so the CPU oracle can replay it exactly.
+//
+// Stream layout (tests/sampler_ref.py restates it; test_sampler_cpu.py pins it):
+//   key     = {seed low word, seed high word}
+//   counter = {block number from 0, view, sample, batch low word ^ batch high word * 0x9E3779B9}
+// The four words of a block are used in order.  Draw order, every draw made for every record
+// whatever the flags come to: per crop try (10 at most) scale (1 word), log-ratio (1), row and
+// column position (1 + 1, drawn even when the try does not fit); then flip (2), jitter (2),
+// op-order shuffle (3), brightness, contrast, saturation, hue (1 each), grayscale (2), blur (2),
+// sigma (2), solarize (2).
 #pragma once
 
 #include <math.h>
