@@ -1,23 +1,36 @@
 // kernels.hip — the gfx950 kernels of the DINO Stage-3 ingest path.
 //
+// One translation unit, in order of definition; what stands in a kernels_*.inc is named with it.
+// Shared device utilities: BlkIdx / xcd_blk / main_prio, block_excl_scan, scan_and_place, item_image
 // Decode half (one JPEG per workgroup where the work is serial per image):
-//   k_parse     1 lane / image      marker parse -> ImgDesc
+//   k_parse     1 wave / image      marker parse -> ImgDesc
 //   k_plan      1 workgroup         per-image workspace offsets (prefix sum), capacity check
-//   k_destuff   256 lanes / image   0xFF00 unstuffing + RSTn removal (block compaction)
+//   k_destuff_count / _write        0xFF00 unstuffing + RSTn removal, persistent over 32 KiB parts
 //   k_htab .. k_huff3                self-synchronising speculative Huffman decode in
 //                                   work items of 256 lanes (see the Huffman section)
-//   k_idct      lanes over blocks   islow IDCT (int32 fast path, int64 exact fallback)
+//   k_pwalk, k_pscan                coefficient-buffer images (progressive ...): the wave decoder
+//   k_plscan, k_papply              the same images on the lane decoder (opt-in)
+//   k_dcscan                        DC predictors of a speculatively decoded image
+//   k_idct      8 lanes / block     islow IDCT in libjpeg-turbo's SIMD arithmetic
 //   k_color     lanes over pixels   fancy upsampling + YCbCr->RGB
 //   k_idct4 / k_color4              the same for four-component frames (CMYK / YCCK), launched
 //                                   only by a context with dino_ctx_set_four_component on
 // Augment half (per view):
-//   k_params    1 lane / view       Philox draw of the view record (optional)
-//   k_vplan     1 workgroup         per-view scratch offsets
-//   k_rcoeffs   lanes over outputs  Pillow coefficient tables of the context's filter (both axes)
-//   k_hresize   lanes over pixels   horizontal pass (crop rows -> S columns, u8)
-//   k_augment   1 workgroup / view  vertical pass -> LDS planes -> jitter -> gray
-//                                   -> blur + solarize + normalize -> NCHW output
-// Plus k_masks (iBOT) and k_bf16_to_fp8 (Stage 5).
+//   kernels_view_plan.inc           k_params (Philox draw of the view record, optional), k_vsizes,
+//                                   k_vplan (per-view scratch offsets), k_rcoeffs (Pillow
+//                                   coefficient tables of the context's filter, both axes)
+//   kernels_hresize.inc             k_hresize: horizontal pass (crop rows -> S columns, u8)
+//   k_vert, k_final                 vertical pass + jitter ops before contrast; contrast, the later
+//                                   ops, gray, blur, solarize, normalise, cast -> NCHW output
+//   k_vfinal                        the two fused through an LDS tile (views up to 128)
+// Then:
+//   kernels_decode_only.inc         k_dplan, k_dcoeffs, k_dhpass, k_dvpass: whole-image resize
+//   kernels_small.inc               k_masks (iBOT), k_bf16_to_fp8 (Stage 5), k_copy_rgb*, k_info
+//   kernels_timer.inc               host: KernelTimer, DINO_SYNC_CHECK
+//   kernels_png.inc                 k_pnghead, k_pngwalk, k_inflate, k_unfilter (opt-in)
+//   kernels_launch.inc              host: init_launch_geom and every launch_*; k_pixel_ops
+// A fragment is text of this file, inside namespace dino: it includes nothing, is never compiled
+// on its own, and may use whatever stands before it.
 #include "augment.hpp"
 #include "color.hpp"
 #include "huffman.hpp"
@@ -198,6 +211,23 @@ __device__ __forceinline__ void scan_and_place(int n, int64_t cap, Size size, Pl
   }
 }
 
+// The persistent kernels' work items (destuff parts, Huffman segments): image i owns the
+// items [desc[i].*Base, + desc[i].*Count) of the batch, in batch order.  The image of `item`:
+// the last one whose base is <= item, stepping back over images without items; -1 past the end.
+template <int32_t ImgDesc::*Base, int32_t ImgDesc::*Count>
+__device__ __forceinline__ int item_image(const ImgDesc* desc, int B, int item) {
+  const ImgDesc& last = desc[B - 1];
+  if (item >= last.*Base + last.*Count) return -1;
+  int lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (desc[mid].*Base <= item) lo = mid;
+    else hi = mid - 1;
+  }
+  while (lo > 0 && desc[lo].*Count == 0) --lo;
+  return lo;
+}
+
 // ---------------------------------------------------------------------------
 // k_plan: exclusive scan of per-image chunk sizes (single workgroup of 1024)
 // ---------------------------------------------------------------------------
@@ -371,16 +401,7 @@ __device__ __forceinline__ DsGeom ds_geom(const uint8_t* bytes, const int64_t* o
 
 // Work item -> (image, part) over desc[].ds_item_base (k_plan); -1 past the end.
 __device__ int ds_item_image(const ImgDesc* desc, int B, int item) {
-  const ImgDesc& last = desc[B - 1];
-  if (item >= last.ds_item_base + last.ds_items) return -1;
-  int lo = 0, hi = B - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (desc[mid].ds_item_base <= item) lo = mid;
-    else hi = mid - 1;
-  }
-  while (lo > 0 && desc[lo].ds_items == 0) --lo;
-  return lo;
+  return item_image<&ImgDesc::ds_item_base, &ImgDesc::ds_items>(desc, B, item);
 }
 
 // Per-part results of k_destuff_count: kept bytes, RST markers, first terminator.
@@ -838,18 +859,9 @@ __global__ void __launch_bounds__(1024) k_hseg(ImgDesc* __restrict__ desc, int B
   }
 }
 
-// Image owning work item `item` (binary search over h_item_base); -1 past the end.
+// Image owning work item `item` (search over h_item_base, k_hseg); -1 past the end.
 __device__ int huff_item_image(const ImgDesc* desc, int B, int item) {
-  const ImgDesc& last = desc[B - 1];
-  if (item >= last.h_item_base + last.h_items) return -1;
-  int lo = 0, hi = B - 1;
-  while (lo < hi) {  // last image with h_item_base <= item and h_items > 0
-    const int mid = (lo + hi + 1) >> 1;
-    if (desc[mid].h_item_base <= item) lo = mid;
-    else hi = mid - 1;
-  }
-  while (lo > 0 && desc[lo].h_items == 0) --lo;
-  return lo;
+  return item_image<&ImgDesc::h_item_base, &ImgDesc::h_items>(desc, B, item);
 }
 
 // An image of one segment without restart intervals and with short lane ranges is
@@ -2757,473 +2769,8 @@ __global__ void __launch_bounds__(256) k_color(const uint8_t* __restrict__ bytes
   }
 }
 
-// ---------------------------------------------------------------------------
-// Augment half
-// ---------------------------------------------------------------------------
-__global__ void k_params(const ImgDesc* __restrict__ desc, int B, dino_aug_config cfg, uint64_t seed,
-                         uint64_t batch_index, dino_view_params* __restrict__ out) {
-  const int nv = cfg.n_global + cfg.n_local;
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * nv) return;
-  int b = i / nv, v = i - b * nv;
-  const ImgDesc& d = desc[b];
-  int ok = d.status == DINO_IMG_OK;
-  if (!ok && d.status < 0 && cfg.recipe == DINO_RECIPE_LEJEPA) {
-    // CPULeJEPAPipeline (cpu.py:446-448) crops an undecodable image's views from a black
-    // 224 x 224 canvas: the draws are those of that canvas (k_final writes its values)
-    sample_view(cfg, seed, batch_index, b, v, 224, 224, 1, &out[i]);
-    return;
-  }
-  sample_view(cfg, seed, batch_index, b, v, ok ? d.width : 1, ok ? d.height : 1, ok, &out[i]);
-}
-
-// Resample target of a view's crop box (0 in the record means the view size S).
-__device__ __forceinline__ int view_rw(const dino_view_params& p) { return p.resize_w > 0 ? p.resize_w : p.out_size; }
-__device__ __forceinline__ int view_rh(const dino_view_params& p) { return p.resize_h > 0 ? p.resize_h : p.out_size; }
-
-// Host-supplied records are validated before any kernel indexes memory with them.
-__device__ bool params_valid(const dino_view_params& p, const ImgDesc& d, int S) {
-  if (p.out_size != S) return false;
-  if (p.crop_top < 0 || p.crop_left < 0 || p.crop_h < 1 || p.crop_w < 1) return false;
-  if ((int64_t)p.crop_top + p.crop_h > d.height || (int64_t)p.crop_left + p.crop_w > d.width) return false;
-  if (p.blur && (p.ksize < 1 || p.ksize > 15 || (p.ksize & 1) == 0 || !(p.sigma > 0.0) || p.ksize / 2 >= S))
-    return false;  // torch reflect padding needs pad < S
-  for (int k = 0; k < 4; ++k)
-    if (p.order[k] > 3) return false;
-  // window of the resampled box: inside it, and an axis that is not resampled has no window
-  const int rw = view_rw(p), rh = view_rh(p);
-  if (rw < S || rh < S || rw > 65536 || rh > 65536 || p.out_x < 0 || p.out_y < 0) return false;
-  if (p.out_x + S > rw || p.out_y + S > rh) return false;
-  if (p.crop_w == rw && (rw != S || p.out_x != 0)) return false;
-  if (p.crop_h == rh && (rh != S || p.out_y != 0)) return false;
-  return true;
-}
-
-// k_vsizes: one lane per view: validity and scratch bytes into plan[i] (htmp_off holds
-// the size and rcoef_off the offset of the coefficient tables inside it until k_vplan
-// places the view), so that the single-workgroup scan only reads packed records.
-__global__ void __launch_bounds__(256) k_vsizes(const ImgDesc* __restrict__ desc, const dino_view_params* __restrict__ prm,
-                                                int B, int nv, int n_global, int gsize, int lsize, int filter,
-                                                ViewPlan* __restrict__ plan) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * nv) return;
-  const ImgDesc& d = desc[i / nv];
-  const int S = (i % nv) < n_global ? gsize : lsize;
-  const int ok = d.status == DINO_IMG_OK && params_valid(prm[i], d, S);
-  const dino_view_params& p = prm[i];
-  const int32_t kh = ok && p.crop_w != view_rw(p) ? resample_ksize(p.crop_w, view_rw(p), filter) : 0;
-  const int32_t kv = ok && p.crop_h != view_rh(p) ? resample_ksize(p.crop_h, view_rh(p), filter) : 0;
-  const ViewScratch L = view_scratch(S, p.crop_h, kh, kv);
-  ViewPlan vp;
-  vp.ok = ok;
-  vp.lsum = 0;
-  vp.kh = kh;
-  vp.kv = kv;
-  vp.htmp_off = ok ? L.total : 0;  // 0: the view is not rendered
-  vp.rcoef_off = L.hb;
-  // (a vertical-first view is resampled by k_rcoeffs: no k_hresize items)
-  const bool vfirst = ok && resample_vfirst(p.crop_w, p.crop_h, view_rh(p), kh);
-  vp.hr_chunks = ok && kh && !vfirst ? hr_view_chunks(S, p.crop_w, p.crop_h, kh) : 0;
-  vp.hr_base = 0;
-  plan[i] = vp;
-}
-
-// Per-view scratch offsets and k_hresize work-item bases from k_vsizes' records
-// (scan_and_place).  A view that cannot be placed is not rendered and its image is marked
-// DINO_IMG_NO_SPACE (reported by dino_batch_info; the host sizes the workspace with
-// dino_probe + dino_reserve so that this does not happen on the product path).
-struct ViewSum {
-  int64_t bytes;
-  int32_t hg, hl;  // k_hresize work items of the global / local views
-  __device__ ViewSum operator+(const ViewSum& o) const { return {bytes + o.bytes, hg + o.hg, hl + o.hl}; }
-};
-
-__global__ void __launch_bounds__(1024) k_vplan(ImgDesc* __restrict__ desc, const dino_view_params* __restrict__ prm,
-                                                int B, int nv, int n_global, int gsize, int lsize, int64_t aws_size,
-                                                ViewPlan* __restrict__ plan) {
-  const int t = threadIdx.x, N = B * nv;
-  for (int b = t; b < B; b += 1024) desc[b].aug_status = 0;
-  if (t == 0) plan[N] = ViewPlan{};  // k_hresize's work-item counters (global, local views): hr_chunks, hr_base
-  scan_and_place<ViewSum>(
-      N, aws_size,
-      [&](int i) {  // k_vsizes: htmp_off holds the view's scratch bytes until it is placed
-        const int32_t c = plan[i].hr_chunks;
-        const bool g = (i % nv) < n_global;
-        return ViewSum{plan[i].htmp_off, g ? c : 0, g ? 0 : c};
-      },
-      [&](int i, const ViewSum&, const ViewSum& base, bool placed) {
-        ViewPlan vp = plan[i];
-        vp.ok = vp.ok && placed;
-        vp.htmp_off = base.bytes;
-        vp.rcoef_off += base.bytes;
-        vp.hr_base = (i % nv) < n_global ? base.hg : base.hl;
-        plan[i] = vp;
-      },
-      [&](int i) { desc[i / nv].aug_status = DINO_IMG_NO_SPACE; });
-}
-
-__global__ void __launch_bounds__(256) k_rcoeffs(const ImgDesc* __restrict__ desc, const dino_view_params* __restrict__ prm,
-                                                 const ViewPlan* __restrict__ plan, int nv, int v0, int filter,
-                                                 const uint8_t* __restrict__ ws, uint8_t* __restrict__ aws) {
-  const int i = blockIdx.y * nv + v0 + blockIdx.x;
-  const ViewPlan vp = plan[i];
-  if (!vp.ok) return;
-  const dino_view_params p = prm[i];
-  const int S = p.out_size;
-  const ViewTables<uint8_t*> T = view_tables(aws + vp.rcoef_off, S, vp.kh, vp.kv);
-  int32_t *hb = (int32_t*)T.hb, *vb = (int32_t*)T.vb, *ht = (int32_t*)T.ht, *vt = (int32_t*)T.vt;
-  int4* hx = (int4*)T.hx;
-  uint4* hg = (uint4*)T.hg;
-  for (int x = threadIdx.x; x < S; x += blockDim.x) {
-    if (vp.kh) {
-      int32_t* k = ht + (int64_t)x * vp.kh;
-      resample_coeffs_one(p.crop_w, view_rw(p), p.out_x + x, vp.kh, &hb[2 * x], &hb[2 * x + 1], k, filter);
-      // sum_t p_t k_t = sum_t (p_t - 128) k_t + 128 sum_t k_t, and k_t = D0 + 256 D1 + 65536 D2
-      // with signed digits D in [-128, 127] (exact for -2^23 - 2^15 <= k < 2^23 - 2^15 = 1.992 x
-      // 2^22; the largest tap of any filter is LANCZOS's 1.2851 x 2^22, resize.hpp tap_mad): three
-      // v_dot4 products per 4 taps
-      const int cnt = hb[2 * x + 1], ng = (cnt + 3) / 4;
-      int32_t ksum = 0;
-      for (int g = 0; g < ng; ++g) {
-        uint32_t dp[3] = {0u, 0u, 0u};
-        for (int j = 0; j < 4; ++j) {
-          const int t = 4 * g + j;
-          const int32_t kt = t < cnt ? k[t] : 0;
-          ksum += kt;
-          const int32_t d0 = (int32_t)(int8_t)(uint8_t)(kt & 0xFF);
-          const int32_t r1 = (kt - d0) >> 8;
-          const int32_t d1 = (int32_t)(int8_t)(uint8_t)(r1 & 0xFF);
-          const int32_t d2 = (r1 - d1) >> 8;
-          dp[0] |= (uint32_t)(uint8_t)d0 << (8 * j);
-          dp[1] |= (uint32_t)(uint8_t)d1 << (8 * j);
-          dp[2] |= (uint32_t)(uint8_t)d2 << (8 * j);
-        }
-        hg[(int64_t)g * S + x] = make_uint4(dp[0], dp[1], dp[2], 0u);
-      }
-      // k_hresize runs the view's ng_max groups for every output: zero taps past this one's
-      for (int g = ng; g < (vp.kh + 3) / 4; ++g) hg[(int64_t)g * S + x] = make_uint4(0u, 0u, 0u, 0u);
-      hx[x] = make_int4(hb[2 * x], ng, 128 * ksum + (1 << (kPrecisionBits - 1)), 0);
-    }
-    if (vp.kv)
-      resample_coeffs_one(p.crop_h, view_rh(p), p.out_y + x, vp.kv, &vb[2 * x], &vb[2 * x + 1], vt + (int64_t)x * vp.kv,
-                          filter);
-  }
-  if (!resample_vfirst(p.crop_w, p.crop_h, view_rh(p), vp.kh)) return;
-  // Vertical pass first (resample_vfirst: a crop over 100 times as high as wide, which no
-  // RandomResizedCrop draws; Pillow rounds its 8-bit intermediate in this order).  This
-  // workgroup resamples the whole view, an output row at a time: the row's vertical pass over
-  // the crop's columns into LDS, then its horizontal pass into row y of the temp planes,
-  // where k_hresize (which has no items of this view) would have put crop row y.  The
-  // vertical tables then become the identity on those rows, so that k_vert / k_vfinal copy.
-  __shared__ uint8_t s_row[3 * kVFirstMaxW];
-  const ImgDesc& d = desc[blockIdx.y];
-  const int cw = p.crop_w;
-  const int64_t spitch = (int64_t)d.width * 3, cpl = (int64_t)p.crop_h * S;
-  const uint8_t* src = ws + d.rgb_off + (int64_t)p.crop_top * spitch + (int64_t)p.crop_left * 3;
-  uint8_t* tmp = aws + vp.htmp_off;
-  __syncthreads();  // the tables above
-  for (int y = 0; y < S; ++y) {
-    const int ymin = vb[2 * y], ycnt = vb[2 * y + 1];
-    const int32_t* kv = vt + (int64_t)y * vp.kv;
-    for (int e = threadIdx.x; e < 3 * cw; e += blockDim.x) {
-      const uint8_t* q = src + (int64_t)ymin * spitch + e;
-      int32_t acc = 1 << (kPrecisionBits - 1);
-      for (int t = 0; t < ycnt; ++t) acc = tap_mad(q[(int64_t)t * spitch], kv[t], acc);
-      s_row[e] = clip8_acc(acc);
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < 3 * S; e += blockDim.x) {
-      const int c = e / S, x = e - c * S;
-      const int xmin = hb[2 * x], xcnt = hb[2 * x + 1];
-      const int32_t* kk = ht + (int64_t)x * vp.kh;
-      int32_t acc = 1 << (kPrecisionBits - 1);
-      for (int t = 0; t < xcnt; ++t) acc = tap_mad(s_row[3 * (xmin + t) + c], kk[t], acc);
-      tmp[c * cpl + (int64_t)y * S + x] = clip8_acc(acc);
-    }
-    __syncthreads();
-  }
-  for (int y = threadIdx.x; y < S; y += blockDim.x) {
-    vb[2 * y] = y;
-    vb[2 * y + 1] = 1;
-    vt[(int64_t)y * vp.kv] = 1 << kPrecisionBits;
-  }
-}
-
-// Horizontal pass.  A workgroup owns bands of R source rows of one view.  The
-// crop's pixels for those rows are staged in LDS as RGBX words (each lane turns
-// 12 source bytes = 4 pixels into one 16-byte LDS store); the view's taps are
-// staged in LDS too when they fit.  Each lane then resamples one (row, x) with
-// one LDS word per tap and writes the three channels to planar temp rows
-// [3][crop_h][S].  Crops too wide for LDS take a direct (global) path.
-// The tile shape (hresize_tile, hr_view_chunks) is in hresize_tile.hpp.
-constexpr int kHrStageUnroll = 4;  // staging loads in flight per lane (2: 168.0k, 8: 168.8k, 4: 170.2k img/s C2)
-
-// The view of work item c among the nc class views (b, v0 + j), j = view index mod nvc:
-// the last view whose first item is <= c (views without items share their successor's
-// first item).  64-ary search by each wave: two rounds of loads for 4096 views.
-__device__ __forceinline__ int hr_find_view(const ViewPlan* __restrict__ plan, int nv, int v0, int nvc, int nc, int c) {
-  int lo = 0, len = nc;
-  const int lane = threadIdx.x & 63;
-  while (len > 1) {
-    const int step = (len + 63) >> 6;
-    const int cand = lo + lane * step;
-    bool le = false;
-    if (cand < lo + len) {
-      const int b = cand / nvc;
-      le = plan[b * nv + v0 + (cand - b * nvc)].hr_base <= c;
-    }
-    const uint64_t m = __ballot(le);  // bit 0 set: plan[lo].hr_base <= c holds throughout
-    const int last = 63 - __builtin_clzll(m);
-    lo += last * step;
-    len = min(step, len - last * step);
-  }
-  return lo;
-}
-
-// One tile: nr staged rows x the outputs [x0, x0 + sw) of a slice.  Lane (row pair, x)
-// accumulates three signed-dot4 digit products per row, channel and group of 4 taps.
-// Rows are staged with the sign bit flipped (p - 128 as int8) from source column c0,
-// word-interleaved: word (gw, r, c) = 4 pixels gw of row r, channel c at gw * R3p + 3 r + c
-// (R3p = hresize_r3p(R): even, so a row pair's six words are one 8-byte-aligned run: three
-// ds_read_b64 per group and one address for all of them).  The taps' pixels start at xmin,
-// so each group's 4 pixels are one v_alignbyte of a word and the next group's (carried).
-// The group loop runs the view's ng_max groups for every lane (taps past an output's own
-// count are zero digits, k_rcoeffs), a wave-uniform trip count the compiler unrolls for
-// NG <= 8.  Exact: the int32 sum equals Pillow's.
-template <int NG>
-__device__ __forceinline__ void hresize_tile_dot(const uint32_t* __restrict__ rows, int R3p, int nr, int r0, int x0,
-                                                 int sw, int c0, int S, int ng, int ngp, const int4* __restrict__ hx,
-                                                 const uint4* __restrict__ hg, uint8_t* __restrict__ tmp, int64_t cpl) {
-  if (NG) ng = NG;
-  const int npair = (nr + 1) >> 1;
-  const int qs = R3p >> 1;  // uint2 stride per source group
-  // lane task (row pair rp, output xl), advanced by the block size without dividing again
-  const int dq = (int)blockDim.x / sw, dr = (int)blockDim.x - dq * sw;
-  int rp = (int)threadIdx.x / sw, xl = (int)threadIdx.x - rp * sw;
-  for (; rp < npair; rp += dq, xl += dr, (xl >= sw ? (xl -= sw, ++rp) : 0)) {
-    const int ra = 2 * rp;  // rows ra, ra + 1 (a band's odd last row pairs with an unstored row: not written)
-    const int4 h = hx[xl];
-    const int lo = h.x - c0;
-    const uint32_t sh = (uint32_t)(lo & 3);
-    const uint2* q = (const uint2*)(rows + __umul24((uint32_t)(lo >> 2), (uint32_t)R3p) + 3 * ra);
-    uint32_t lw[6];
-    {
-      const uint2 a0 = q[0], a1 = q[1], a2 = q[2];
-      lw[0] = a0.x, lw[1] = a0.y, lw[2] = a1.x, lw[3] = a1.y, lw[4] = a2.x, lw[5] = a2.y;
-    }
-    int32_t acc[6][3];  // digit 0 starts at the rounding + sign-flip correction h.z
-#pragma unroll
-    for (int k = 0; k < 6; ++k) acc[k][0] = h.z, acc[k][1] = acc[k][2] = 0;
-    const uint4* dgp = hg + xl * ngp;  // this output's taps: ngp consecutive groups (immediate offsets)
-#pragma unroll
-    for (int g = 0; g < ng; ++g) {
-      const uint4 dg = dgp[g];
-      const uint2* qn = q + (g + 1) * qs;
-      const uint2 b0 = qn[0], b1 = qn[1], b2 = qn[2];
-      const uint32_t uw[6] = {b0.x, b0.y, b1.x, b1.y, b2.x, b2.y};
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        const int32_t pa = (int32_t)__builtin_amdgcn_alignbyte(uw[k], lw[k], sh);
-        acc[k][0] = __builtin_amdgcn_sdot4(pa, (int32_t)dg.x, acc[k][0], false);
-        acc[k][1] = __builtin_amdgcn_sdot4(pa, (int32_t)dg.y, acc[k][1], false);
-        acc[k][2] = __builtin_amdgcn_sdot4(pa, (int32_t)dg.z, acc[k][2], false);
-        lw[k] = uw[k];
-      }
-    }
-    // int32 wrap-around is harmless: the true sum (Pillow's int32 ss) fits in int32
-    // (clip8_acc as one med3: the sum is < 2^30 unless it clips to 255, and <= 0 clips to 0;
-    // 32-bit offsets: a view's planes hold < 3 x 2^20 x 1024 bytes)
-    const uint32_t ob = (uint32_t)((r0 + ra) * S + x0 + xl);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      if (ra + i >= nr) break;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int k = 3 * i + c;
-        const uint32_t so = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(i * S) + (uint32_t)c * (uint32_t)cpl));
-        const int32_t sum = (int32_t)((uint32_t)acc[k][0] + ((uint32_t)acc[k][1] << 8) + ((uint32_t)acc[k][2] << 16));
-        tmp[ob + so] = (uint8_t)min(max(sum >> kPrecisionBits, 0), 255);
-      }
-    }
-  }
-}
-
-// Horizontal pass in tiles of (slice of outputs) x (band of rows), shaped by
-// hresize_tile: the slice's taps always come from LDS, and the band stages only the
-// source columns the slice reads [xmin(x0), xmin(x1-1) + xcnt(x1-1)), so wide crops
-// take narrower slices to keep >= kHresizeMinRows rows per band.  A persistent grid
-// takes the class's work items (kHrBandsPerItem bands of one slice, hr_view_chunks) in
-// turn: with mixed crop sizes (C3) a fixed number of workgroups per view left the
-// largest views' workgroups running alone at the end of the launch.
-__device__ __forceinline__ void hresize_item(const ImgDesc* __restrict__ desc, const dino_view_params* __restrict__ prm,
-                                             const ViewPlan* __restrict__ plan, int nv, int v0, int nvc, int nc, int c,
-                                             const uint8_t* __restrict__ ws, uint8_t* __restrict__ aws, uint8_t* smem);
-
-#ifndef DINO_HRESIZE_WAVES  // (A/B: minimum waves per SIMD the register allocation must allow)
-#define DINO_HRESIZE_WAVES 1
-#endif
-__global__ void __launch_bounds__(256, DINO_HRESIZE_WAVES) k_hresize(const ImgDesc* __restrict__ desc, const dino_view_params* __restrict__ prm,
-                                                 ViewPlan* __restrict__ plan, int nv, int v0, int nvc, int B,
-                                                 const uint8_t* __restrict__ ws, uint8_t* __restrict__ aws) {
-  main_prio();
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  __shared__ int s_item[2];
-  const int nc = B * nvc;
-  // persistent grid over the class's work items (k_vplan's per-class prefix), taken in turn
-  // from the class's counter (zeroed by k_vplan), the next one fetched while this one runs
-  const ViewPlan vl = plan[(B - 1) * nv + v0 + nvc - 1];
-  const int nitems_all = vl.hr_base + vl.hr_chunks;
-  int* ctr = v0 == 0 ? &plan[B * nv].hr_chunks : &plan[B * nv].hr_base;
-  if (threadIdx.x == 0) s_item[0] = atomicAdd(ctr, 1);
-  __syncthreads();
-  for (int it = 0, c = s_item[0]; c < nitems_all; ++it) {
-    if (threadIdx.x == 0) s_item[(it + 1) & 1] = atomicAdd(ctr, 1);
-    hresize_item(desc, prm, plan, nv, v0, nvc, nc, c, ws, aws, smem);
-    __syncthreads();
-    c = s_item[(it + 1) & 1];
-  }
-}
-
-__device__ __forceinline__ void hresize_item(const ImgDesc* __restrict__ desc, const dino_view_params* __restrict__ prm,
-                                             const ViewPlan* __restrict__ plan, int nv, int v0, int nvc, int nc, int c,
-                                             const uint8_t* __restrict__ ws, uint8_t* __restrict__ aws, uint8_t* smem) {
-  {
-    const int j = hr_find_view(plan, nv, v0, nvc, nc, c);
-    const int b = j / nvc;
-    const int i = b * nv + v0 + (j - b * nvc);
-    const ViewPlan vp = plan[i];
-    if (!vp.ok || !vp.kh) return;  // (no items: not reached)
-    const int item = c - vp.hr_base;
-    const dino_view_params p = prm[i];
-    const ImgDesc& d = desc[b];
-    const int S = p.out_size, W = d.width, cw = p.crop_w, kh = vp.kh;
-    const ViewTables<const uint8_t*> T = view_tables((const uint8_t*)aws + vp.rcoef_off, S, vp.kh, vp.kv);
-    const int32_t *gb = (const int32_t*)T.hb, *gt = (const int32_t*)T.ht;
-    const int4* ghx = (const int4*)T.hx;
-    const uint4* ghg = (const uint4*)T.hg;
-    const uint8_t* rgb = ws + d.rgb_off;
-    uint8_t* tmp = aws + vp.htmp_off;
-    const int64_t cpl = (int64_t)p.crop_h * S;
-    const int ng_max = (kh + 3) / 4;
-    const int ngp = ng_max | 1;  // tap groups per output in LDS: odd, so 16 lanes' b128 reads hit distinct banks
-    const HrTile tl = hresize_tile(S, cw, kh);
-    const int sw = tl.sw, pitch = tl.pitch, R = tl.R, R3p = tl.R3p;
-    if (R < 1) {  // direct path: taps and pixels from global memory (crops too wide for LDS)
-      const SrcView src{rgb + ((int64_t)p.crop_top * W + p.crop_left) * 3, (int64_t)W * 3, 3, 1};
-      const CoefView cv{gb, gt, kh};
-      for (int64_t e = (int64_t)item * blockDim.x + threadIdx.x; e < cpl; e += (int64_t)kHrDirectItems * blockDim.x) {
-        const int r = (int)(e / S), x = (int)(e - (int64_t)r * S);
-        for (int ch = 0; ch < 3; ++ch) tmp[ch * cpl + e] = hresize_at(src, cv, r, x, ch);
-      }
-      return;
-    }
-    // LDS: the staged rows first (an edge output's zero-tap over-read stays inside the rows'
-    // pad), then the slice's taps
-    uint32_t* rows = (uint32_t*)smem;
-    int4* lx = (int4*)(smem + ((hresize_rows_bytes(pitch, R, ng_max) + 15) & ~15));
-    uint4* lg = (uint4*)(lx + sw);
-    const int nbands = (p.crop_h + R - 1) / R;
-    const int nbg = (nbands + kHrBandsPerItem - 1) / kHrBandsPerItem;
-    // the item: slice sl (outputs [x0, x0 + swn)), bands [band0, band1)
-    const int sl = item / nbg;
-    const int band0 = (item - sl * nbg) * kHrBandsPerItem, band1 = min(nbands, band0 + kHrBandsPerItem);
-    const int x0 = sl * sw, swn = min(sw, S - x0);
-    const int c0 = ghx[x0].x & ~3;  // first source column staged (4-aligned within the crop)
-    const int c1 = min(cw, ghx[x0 + swn - 1].x + gb[2 * (x0 + swn - 1) + 1]);
-    const int ngroups = (c1 - c0 + 3) >> 2;  // staged groups of 4 pixels per row
-    // taps of the slice -> LDS (the previous item ended with a barrier)
-    for (int k = threadIdx.x; k < swn; k += blockDim.x) lx[k] = ghx[x0 + k];
-    for (int k = threadIdx.x; k < swn * ng_max; k += blockDim.x) {
-      const int g = k / swn, xl = k - g * swn;
-      lg[xl * ngp + g] = ghg[(int64_t)g * S + x0 + xl];
-    }
-    // staging item e of a band: row e / ngroups, group e % ngroups (12 source bytes = 4
-    // pixels -> one word per channel, de-interleaved by v_perm byte selects, sign bit
-    // flipped).  kHrStageUnroll items per lane in flight: their 16-byte loads are issued
-    // together and waited on once (one item at a time waited a full memory latency per
-    // item: k_hresize 0.95 -> 0.85 ms per C2 step).  (Issuing the next band's first chunk
-    // before this band's dot products, registers held across them, measured slower: 114-147
-    // VGPRs, 3-4 waves per SIMD instead of 5.)
-    const int64_t spitch = (int64_t)W * 3;
-    const int dr = (int)blockDim.x / ngroups, dg = (int)blockDim.x - dr * ngroups;
-    struct Stage {
-      const uint8_t* base;
-      int nst, e, sr, sg;
-    };
-    auto stage_begin = [&](int band) {
-      const int r0 = band * R;
-      Stage st;
-      st.base = rgb + ((int64_t)(p.crop_top + r0) * W + p.crop_left + c0) * 3;
-      st.nst = min(R, p.crop_h - r0) * ngroups;
-      st.e = (int)threadIdx.x;
-      st.sr = (int)threadIdx.x / ngroups;
-      st.sg = (int)threadIdx.x - st.sr * ngroups;
-      return st;
-    };
-    uint4 wv[kHrStageUnroll];
-    uint32_t shv[kHrStageUnroll], dov[kHrStageUnroll];
-    auto stage_issue = [&](Stage& st) {  // loads of the chunk at st.e (none past the band)
-#pragma unroll
-      for (int u = 0; u < kHrStageUnroll; ++u) {
-        const bool ok = st.e + u * (int)blockDim.x < st.nst;
-        // past the band: load the band's first words again (in bounds), nothing is stored
-        const uint8_t* src = ok ? st.base + st.sr * spitch + 12 * st.sg : st.base;
-        const uint32_t mis = (uint32_t)((uintptr_t)src & 3);
-        wv[u] = *(const uint4*)(src - mis);
-        shv[u] = ok ? 8u * mis : 0xFFFFFFFFu;
-        dov[u] = (uint32_t)(st.sg * R3p + 3 * st.sr);
-        st.sr += dr;
-        st.sg += dg;
-        if (st.sg >= ngroups) st.sg -= ngroups, ++st.sr;
-      }
-      st.e += kHrStageUnroll * (int)blockDim.x;
-    };
-    auto stage_commit = [&]() {
-#pragma unroll
-      for (int u = 0; u < kHrStageUnroll; ++u) {
-        if (shv[u] == 0xFFFFFFFFu) break;
-        const uint32_t sh = shv[u];
-        const uint32_t q0 = (uint32_t)((((uint64_t)wv[u].y << 32) | wv[u].x) >> sh);  // R0 G0 B0 R1
-        const uint32_t q1 = (uint32_t)((((uint64_t)wv[u].z << 32) | wv[u].y) >> sh);  // G1 B1 R2 G2
-        const uint32_t q2 = (uint32_t)((((uint64_t)wv[u].w << 32) | wv[u].z) >> sh);  // B2 R3 G3 B3
-        const uint32_t cr = __builtin_amdgcn_perm(q2, __builtin_amdgcn_perm(q1, q0, 0x0C060300u), 0x05020100u);
-        const uint32_t cg = __builtin_amdgcn_perm(q2, __builtin_amdgcn_perm(q1, q0, 0x0C070401u), 0x06020100u);
-        const uint32_t cb = __builtin_amdgcn_perm(q2, __builtin_amdgcn_perm(q1, q0, 0x0C0C0502u), 0x07040100u);
-        uint32_t* dst = rows + dov[u];
-        dst[0] = cr ^ 0x80808080u;
-        dst[1] = cg ^ 0x80808080u;
-        dst[2] = cb ^ 0x80808080u;
-      }
-    };
-    for (int band = band0; band < band1; ++band) {
-      const int r0 = band * R, nr = min(R, p.crop_h - r0);
-      Stage st = stage_begin(band);
-      while (st.e < st.nst) {
-        stage_issue(st);
-        stage_commit();
-      }
-      __syncthreads();
-      switch (ng_max) {
-#define DINO_HR_CASE(N) \
-  case N: \
-    hresize_tile_dot<N>(rows, R3p, nr, r0, x0, swn, c0, S, ng_max, ngp, lx, lg, tmp, cpl); \
-    break;
-        DINO_HR_CASE(1)
-        DINO_HR_CASE(2)
-        DINO_HR_CASE(3)
-        DINO_HR_CASE(4)
-        DINO_HR_CASE(5)
-        DINO_HR_CASE(6)
-        DINO_HR_CASE(7)
-        DINO_HR_CASE(8)
-#undef DINO_HR_CASE
-        default:
-          hresize_tile_dot<0>(rows, R3p, nr, r0, x0, swn, c0, S, ng_max, ngp, lx, lg, tmp, cpl);
-      }
-      __syncthreads();
-    }
-  }
-}
+#include "kernels_view_plan.inc"
+#include "kernels_hresize.inc"
 
 // Per-view slot of the u8 crop planes [3][S][S] (global views first, then local views).
 __device__ __forceinline__ int64_t crop_slot(const dino_aug_config& cfg, int B, int b, int v) {
@@ -3958,733 +3505,10 @@ __global__ void __launch_bounds__(kVFinalThreads) k_vfinal(const ImgDesc* __rest
   }
 }
 
-// ---------------------------------------------------------------------------
-// Decode-only recipe (reference CPUUserAugPipeline, cpu.py:484-500; DALI
-// _build_decode_only_pipeline, pipeline.py:693-756): every image of the batch
-// resampled whole (Pillow BICUBIC or the context's filter, horizontal pass then vertical, each only when
-// that axis changes size) to ow x oh, normalised and cast, NCHW.  Scratch per
-// image (k_dplan, the ViewPlan slot of view 0): coefficient tables of both axes +
-// the horizontal pass's rows (planar u8 [3][H][ow]).
-// ---------------------------------------------------------------------------
-// The image's scratch layout (zero bytes when it did not decode) and tap counts.
-__device__ DecScratch<int64_t> dec_layout(const ImgDesc& d, int ow, int oh, int filter, int32_t* kh, int32_t* kv) {
-  const bool ok = d.status == DINO_IMG_OK;
-  *kh = ok && d.width != ow ? resample_ksize(d.width, ow, filter) : 0;
-  *kv = ok && d.height != oh ? resample_ksize(d.height, oh, filter) : 0;
-  return ok ? dec_scratch((int64_t)0, ow, oh, d.height, *kh, *kv) : DecScratch<int64_t>{};
-}
-
-struct DecSum {
-  int64_t bytes;
-  __device__ DecSum operator+(const DecSum& o) const { return {bytes + o.bytes}; }
-};
-
-__global__ void __launch_bounds__(1024) k_dplan(ImgDesc* __restrict__ desc, int B, int ow, int oh, int filter,
-                                                int64_t aws_size, ViewPlan* __restrict__ plan) {
-  for (int b = threadIdx.x; b < B; b += 1024) desc[b].aug_status = 0;
-  scan_and_place<DecSum>(
-      B, aws_size,
-      [&](int i) {
-        int32_t kh, kv;
-        return DecSum{dec_layout(desc[i], ow, oh, filter, &kh, &kv).total};
-      },
-      [&](int i, const DecSum&, const DecSum& base, bool placed) {
-        ViewPlan vp{};
-        const DecScratch<int64_t> L = dec_layout(desc[i], ow, oh, filter, &vp.kh, &vp.kv);
-        vp.ok = placed && L.total != 0;
-        vp.rcoef_off = base.bytes;
-        vp.htmp_off = base.bytes + L.htmp;
-        plan[i] = vp;
-      },
-      [&](int i) { desc[i].aug_status = DINO_IMG_NO_SPACE; });
-}
-
-__global__ void __launch_bounds__(256) k_dcoeffs(const ImgDesc* __restrict__ desc, const ViewPlan* __restrict__ plan,
-                                                 int ow, int oh, int filter, uint8_t* __restrict__ aws) {
-  const int b = blockIdx.x;
-  const ViewPlan vp = plan[b];
-  if (!vp.ok) return;
-  const ImgDesc& d = desc[b];
-  const DecScratch<uint8_t*> L = dec_scratch(aws + vp.rcoef_off, ow, oh, d.height, vp.kh, vp.kv);
-  int32_t *hb = (int32_t*)L.hb, *ht = (int32_t*)L.ht, *vb = (int32_t*)L.vb, *vt = (int32_t*)L.vt;
-  if (vp.kh)
-    for (int x = threadIdx.x; x < ow; x += blockDim.x)
-      resample_coeffs_one(d.width, ow, x, vp.kh, &hb[2 * x], &hb[2 * x + 1], ht + (int64_t)x * vp.kh, filter);
-  if (vp.kv)
-    for (int y = threadIdx.x; y < oh; y += blockDim.x)
-      resample_coeffs_one(d.height, oh, y, vp.kv, &vb[2 * y], &vb[2 * y + 1], vt + (int64_t)y * vp.kv, filter);
-}
-
-__global__ void __launch_bounds__(256) k_dhpass(const ImgDesc* __restrict__ desc, const ViewPlan* __restrict__ plan,
-                                                int ow, const uint8_t* __restrict__ ws, uint8_t* __restrict__ aws) {
-  const int b = blockIdx.y;
-  const ViewPlan vp = plan[b];
-  if (!vp.ok || !vp.kh) return;
-  const ImgDesc& d = desc[b];
-  const DecHTables<const uint8_t*> L = dec_htables((const uint8_t*)aws + vp.rcoef_off, ow);
-  const CoefView cv{(const int32_t*)L.hb, (const int32_t*)L.ht, vp.kh};
-  const SrcView src{ws + d.rgb_off, (int64_t)d.width * 3, 3, 1};
-  uint8_t* tmp = aws + vp.htmp_off;
-  const int64_t n = (int64_t)d.height * ow, plane = n;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-    const int y = (int)(e / ow), x = (int)(e - (int64_t)y * ow);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) tmp[c * plane + e] = hresize_at(src, cv, y, x, c);
-  }
-}
-
-template <typename OutT>
-__global__ void __launch_bounds__(256) k_dvpass(const ImgDesc* __restrict__ desc, const ViewPlan* __restrict__ plan,
-                                                int ow, int oh, const uint8_t* __restrict__ ws,
-                                                const uint8_t* __restrict__ aws, OutT* __restrict__ out, float m0,
-                                                float m1, float m2, float s0, float s1, float s2,
-                                                const float* __restrict__ norm) {
-  const int b = blockIdx.y;
-  const ViewPlan vp = plan[b];
-  const ImgDesc& d = desc[b];
-  const int64_t n = (int64_t)oh * ow;
-  OutT* o = out + (int64_t)b * 3 * n;
-  const float* nb = norm ? norm + (int64_t)b * 6 : nullptr;
-  const float mean[3] = {nb ? nb[0] : m0, nb ? nb[1] : m1, nb ? nb[2] : m2};
-  const float stdv[3] = {nb ? nb[3] : s0, nb ? nb[4] : s1, nb ? nb[5] : s2};
-  if (!vp.ok) {  // undecodable (cpu.py:496-497) or not placed: zeros
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < 3 * n; e += (int64_t)gridDim.x * blockDim.x)
-      o[e] = (OutT)0;
-    return;
-  }
-  const DecScratch<const uint8_t*> L = dec_scratch(aws + vp.rcoef_off, ow, oh, d.height, vp.kh, vp.kv);
-  const CoefView cv{(const int32_t*)L.vb, (const int32_t*)L.vt, vp.kv};
-  const SrcView src = vp.kh ? SrcView{aws + vp.htmp_off, (int64_t)ow, 1, (int64_t)d.height * ow}
-                            : SrcView{ws + d.rgb_off, (int64_t)d.width * 3, 3, 1};
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-    const int y = (int)(e / ow), x = (int)(e - (int64_t)y * ow);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int v = vp.kv ? vresize_at(src, cv, y, x, c)
-                          : src.base[(int64_t)y * src.pitch + (int64_t)x * src.px + c * src.cs];
-      o[c * n + e] = out_cast<OutT>(u8_normalize(v, mean[c], stdv[c]));
-    }
-  }
-}
-
-template <typename OutT>
-static hipError_t launch_dec_out(const DecodeOnlyArgs& a, hipStream_t s) {
-  const int gx = 64;
-  k_dvpass<OutT><<<dim3(gx, a.batch), 256, 0, s>>>(a.desc, a.plan, a.ow, a.oh, a.ws, a.aws, (OutT*)a.out, a.mean[0],
-                                                   a.mean[1], a.mean[2], a.std[0], a.std[1], a.std[2], a.norm);
-  return hipGetLastError();
-}
-
-hipError_t launch_decode_only(const DecodeOnlyArgs& a, hipStream_t s) {
-  if (a.batch <= 0) return hipSuccess;
-  k_dplan<<<1, 1024, 0, s>>>(a.desc, a.batch, a.ow, a.oh, a.filter, a.aws_size, a.plan);
-  k_dcoeffs<<<a.batch, 256, 0, s>>>(a.desc, a.plan, a.ow, a.oh, a.filter, a.aws);
-  k_dhpass<<<dim3(64, a.batch), 256, 0, s>>>(a.desc, a.plan, a.ow, a.ws, a.aws);
-  switch (a.out_dtype) {
-    case DINO_OUT_FP32: return launch_dec_out<float>(a, s);
-    case DINO_OUT_FP8_E4M3: return launch_dec_out<uint8_t>(a, s);
-    default: return launch_dec_out<uint16_t>(a, s);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// iBOT masks: one lane runs the (inherently sequential) generator; the mask and
-// the completion scratch live in LDS (dynamic, 5 bytes per patch), the MT states too.
-// ---------------------------------------------------------------------------
-constexpr int kMaskLdsMaxPatches = 8192;  // 40 KiB of dynamic LDS (grids up to 90 x 90)
-
-__global__ void k_masks(MaskParams mp, int n, uint32_t* __restrict__ py_state, uint32_t* __restrict__ np_state,
-                        uint8_t* __restrict__ out) {
-  __shared__ MtState py, np;
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const int hw = mp.H * mp.W;
-  int32_t* scratch = reinterpret_cast<int32_t*>(smem);
-  uint8_t* mask = smem + 4 * hw;
-  if (threadIdx.x == 0) {
-    mt_load(py, py_state);
-    mt_load(np, np_state);
-  }
-  __syncthreads();
-  for (int k = 0; k < n; ++k) {
-    if (threadIdx.x == 0) gen_mask(mp, py, np, mask, scratch);
-    __syncthreads();
-    for (int i = threadIdx.x; i < hw; i += blockDim.x) out[(int64_t)k * hw + i] = mask[i];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    mt_store(py, py_state);
-    mt_store(np, np_state);
-  }
-}
-
-__global__ void k_bf16_to_fp8(const uint16_t* __restrict__ in, uint8_t* __restrict__ out, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = f32_to_fp8e4m3(bf16_to_f32(in[i]));
-}
-
-// copy of one decoded image out of the workspace (tests / debug)
-__global__ void k_copy_rgb(const ImgDesc* __restrict__ desc, int idx, const uint8_t* __restrict__ ws,
-                           uint8_t* __restrict__ dst) {
-  const ImgDesc& d = desc[idx];
-  if (d.status != DINO_IMG_OK) return;
-  const int64_t n = (int64_t)d.width * d.height * 3;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    dst[i] = ws[d.rgb_off + i];
-}
-
-// Decoded images -> raw containers (the side decoder): image idx[k]'s RGB to base + off[k]
-// (base null: off[k] is the destination's device address), grid (x, n).  16-byte copies when
-// source and destination are both 16-byte aligned (the workspace's RGB areas are; the
-// containers' data starts 16 bytes into a 16-byte aligned slice), the tail and unaligned
-// cases bytewise.  With `header`, the 16 bytes before the data get the container header
-// {DINO_RAW_MAGIC, width, height, 0} (little-endian words).
-__global__ void k_copy_rgb_packed(const ImgDesc* __restrict__ desc, int B, const int32_t* __restrict__ idx,
-                                  const int64_t* __restrict__ off, const uint8_t* __restrict__ ws,
-                                  uint8_t* __restrict__ base, int header) {
-  const int k = blockIdx.y, i = idx[k];
-  if (i < 0 || i >= B) return;
-  const ImgDesc& d = desc[i];
-  if (d.status != DINO_IMG_OK) return;
-  const int64_t n = (int64_t)d.width * d.height * 3;
-  const uint8_t* src = ws + d.rgb_off;
-  uint8_t* dst = base ? base + off[k] : reinterpret_cast<uint8_t*>(static_cast<uintptr_t>(off[k]));
-  if (header && blockIdx.x == 0 && threadIdx.x < 16) {
-    const uint32_t w[4] = {DINO_RAW_MAGIC, (uint32_t)d.width, (uint32_t)d.height, 0u};
-    const int j = threadIdx.x;
-    dst[j - 16] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
-  }
-  const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, ts = (int64_t)gridDim.x * blockDim.x;
-  int64_t head = 0;
-  if ((((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
-    const int64_t n16 = n >> 4;
-    for (int64_t q = t0; q < n16; q += ts) ((uint4*)dst)[q] = ((const uint4*)src)[q];
-    head = n16 << 4;
-  }
-  for (int64_t q = head + t0; q < n; q += ts) dst[q] = src[q];
-}
-
-__global__ void k_info(const ImgDesc* __restrict__ desc, int B, int32_t* __restrict__ info) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  const ImgDesc& d = desc[i];
-  info[4 * i + 0] = d.status != DINO_IMG_OK ? d.status : d.aug_status;
-  info[4 * i + 1] = d.width;
-  info[4 * i + 2] = d.height;
-  info[4 * i + 3] = d.ncomp;
-}
-
-
-}  // namespace dino
-
-// ===========================================================================
-// Launchers
-// ===========================================================================
-namespace dino {
-
-void KernelTimer::begin(int k, hipStream_t s) {
-  if (!enabled) return;
-  if (!created) {
-    for (int i = 0; i < kMaxPending; ++i) {
-      (void)hipEventCreate(&ev[i][0]);
-      (void)hipEventCreate(&ev[i][1]);
-    }
-    created = true;
-    reset();
-  }
-  if (n >= kMaxPending) collect();
-  id[n] = k;
-  (void)hipEventRecord(ev[n][0], s);
-}
-
-void KernelTimer::end(hipStream_t s) {
-  if (!enabled || !created) return;
-  (void)hipEventRecord(ev[n][1], s);
-  ++n;
-}
-
-void KernelTimer::collect() {
-  for (int i = 0; i < n; ++i) {
-    float ms = 0.f;
-    (void)hipEventSynchronize(ev[i][1]);
-    if (hipEventElapsedTime(&ms, ev[i][0], ev[i][1]) == hipSuccess) {
-      total_ms[id[i]] += ms;
-      count[id[i]] += 1;
-    }
-  }
-  n = 0;
-}
-
-void KernelTimer::reset() {
-  n = 0;
-  for (int i = 0; i < kKNumKernels; ++i) {
-    total_ms[i] = 0.0;
-    count[i] = 0;
-  }
-}
-
-void KernelTimer::destroy() {
-  if (!created) return;
-  for (int i = 0; i < kMaxPending; ++i) {
-    (void)hipEventDestroy(ev[i][0]);
-    (void)hipEventDestroy(ev[i][1]);
-  }
-  created = false;
-}
-
-// DINO_SYNC_CHECK=1: synchronise after every kernel and report which one failed
-// (debugging aid; pinpoints a faulting kernel instead of a later sync point).
-static const bool g_sync_check = [] {
-  const char* v = getenv("DINO_SYNC_CHECK");
-  return v && v[0] == '1';
-}();
-// ---------------------------------------------------------------------------
-// PNG (kind 4): k_pnghead -> k_pngwalk -> k_inflate -> k_unfilter
-// ---------------------------------------------------------------------------
-// Launched only by a context with dino_ctx_set_png on (no other context has a kind-4 image).
-// The image's regions (plan.hpp image_chunk_bytes): ent = the IDAT payloads joined into one
-// zlib stream, plane = the inflated, still-filtered rows, coef = one reconstructed row carried
-// from a band of 64 rows to the next, htab = the palette, rgb = the pixels.
-
-// One lane per image, between k_parse and k_plan: a file with the PNG signature, which k_parse
-// left DINO_IMG_CORRUPT with a cleared descriptor, gets the descriptor of parse_png_head (the
-// signature and IHDR; the chunk walk is k_pngwalk's).  A kernel of its own so that k_parse stays
-// the code it was.
-__global__ void __launch_bounds__(64) k_pnghead(const uint8_t* __restrict__ bytes, const int64_t* __restrict__ offsets,
-                                                const int64_t* __restrict__ lengths, const uint8_t* __restrict__ raw_mask,
-                                                int B, int max_dim, ImgDesc* __restrict__ desc) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= B || (raw_mask != nullptr && raw_mask[i] != 0)) return;
-  const int64_t off = offsets[i], len = lengths ? lengths[i] : offsets[i + 1] - off;
-  if (!png_signature(bytes + off, len)) return;
-  parse_png_head(bytes + off, len, max_dim, &desc[i]);
-}
-
-// One workgroup per image.  Lane 0 walks the chunks (png_walk: CRCs, PLTE / tRNS rules, the
-// IDAT run and what follows it); then all lanes step through the run together and join the
-// payloads, whole destination words where a chunk covers them and bytes at its edges (chunks of
-// length 0 and 1 have only edges).  Fills the palette (zeros past PLTE) and ent_len, and zeroes
-// the ticket counter of k_inflate.
-constexpr int kPngWalkThreads = 256;
-__global__ void __launch_bounds__(kPngWalkThreads) k_pngwalk(const uint8_t* __restrict__ bytes,
-                                                             const int64_t* __restrict__ offsets,
-                                                             const int64_t* __restrict__ lengths, ImgDesc* __restrict__ desc,
-                                                             uint8_t* __restrict__ ws, PCtl* __restrict__ pctl) {
-  __shared__ PngWalk s_w;
-  __shared__ int s_status;
-  const int img = blockIdx.x, tid = threadIdx.x;
-  if (img == 0 && tid == 0) pctl->pad = 0;
-  ImgDesc& d = desc[img];
-  if (d.status != DINO_IMG_OK || d.kind != kPngKind) return;
-  const int64_t off = offsets[img], len = lengths ? lengths[img] : offsets[img + 1] - off;
-  const uint8_t* src = bytes + off;
-  if (tid == 0) s_status = png_walk(src, len, d.color, &s_w);
-  __syncthreads();
-  if (s_status != DINO_IMG_OK) {
-    if (tid == 0) d.status = s_status;
-    return;
-  }
-  uint8_t* pal = ws + d.htab_off;
-  for (int i = tid; i < kPngPalBytes; i += kPngWalkThreads) pal[i] = i < s_w.plte_n ? src[s_w.plte_off + i] : (uint8_t)0;
-  uint8_t* ent = ws + d.ent_off;
-  const int64_t cap = d.rst_off - d.ent_off;  // align16(scan_len + 64) >= the payloads + 64
-  int64_t pos = s_w.idat_off, o = 0;
-  if (s_w.idat_bytes + 64 > cap) {  // (cannot happen: the payloads lie inside the scan_len bytes)
-    if (tid == 0) d.status = DINO_IMG_CORRUPT;
-    return;
-  }
-  for (int c = 0; c < s_w.idat_chunks; ++c) {
-    const int64_t n = rd32be(src + pos);
-    const uint8_t* q = src + pos + 8;
-    const int64_t head = min(n, (int64_t)((4 - (o & 3)) & 3)), nw = (n - head) >> 2;
-    if (tid < head) ent[o + tid] = q[tid];
-    uint32_t* dw = (uint32_t*)(ent + o + head);
-    for (int64_t k = tid; k < nw; k += kPngWalkThreads) {
-      const uint8_t* s = q + head + 4 * k;
-      dw[k] = (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | ((uint32_t)s[3] << 24);
-    }
-    const int64_t t0 = head + 4 * nw;
-    if (t0 + tid < n) ent[o + t0 + tid] = q[t0 + tid];
-    o += n;
-    pos += 12 + n;
-  }
-  if (tid < 64) ent[o + tid] = 0;
-  if (tid == 0) d.ent_len = (int32_t)o;
-}
-
-// One wave per image, persistent: a wave takes the next batch index as its ticket and inflates
-// that image if it is a PNG (inflate.hpp, the code of the host model with nl = 64).  The wave's
-// LDS holds the 32 KiB history ring, a 1 KiB input ring refilled by all lanes with 16-byte
-// loads, both lookahead tables and the code lengths: kInfLdsBytes, four waves per CU.  The ring
-// is flushed to the image's plane region 16 KiB at a time in aligned 16-byte stores; matches
-// read the ring only, never the flushed bytes.
-constexpr int kInfRing = 1024;
-struct InfLds {
-  __attribute__((aligned(16))) uint8_t win[kInfWin];
-  __attribute__((aligned(16))) uint8_t ring[kInfRing];
-  InfTab lt, dt;
-  uint8_t lens[kInfMaxLens];
-};
-constexpr int kInfLdsBytes = (int)sizeof(InfLds);
-static_assert(kInfLdsBytes <= 40 * 1024, "four inflate waves per CU");
-
-struct InfDevIO {
-  int lane, nl;
-  const uint8_t* z;  // the stream's region (16-byte aligned), zcap bytes
-  int64_t zcap, ring_base;
-  uint8_t* ring;
-  uint8_t* out;      // the inflated region (16-byte aligned), out_cap bytes
-  int64_t out_cap;
-  uint8_t* win;
-  InfTab *lt, *dt;
-  uint8_t* lens;
-  __device__ __forceinline__ void sync() { __syncthreads(); }
-  __device__ __forceinline__ uint32_t in(int64_t i) {
-    if (i < ring_base || i >= ring_base + kInfRing) {  // uniform
-      ring_base = i & ~(int64_t)15;
-      __syncthreads();
-      const int64_t at = ring_base + 16 * lane;
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (at >= 0 && at + 16 <= zcap) v = *(const uint4*)(z + at);
-      *(uint4*)(ring + 16 * lane) = v;
-      __syncthreads();
-    }
-    return ring[i - ring_base];
-  }
-  __device__ __forceinline__ void flush(int64_t at, int n) {
-    for (int j = 16 * lane; j < n; j += 16 * 64)
-      if (at + j + 16 <= out_cap) *(uint4*)(out + at + j) = *(const uint4*)(win + ((at + j) & (kInfWin - 1)));
-  }
-};
-
-__global__ void __launch_bounds__(64) k_inflate(ImgDesc* __restrict__ desc, uint8_t* __restrict__ ws, PCtl* __restrict__ pctl,
-                                                int B) {
-  __shared__ InfLds L;
-  __shared__ uint32_t s_ticket;
-  for (;;) {
-    __syncthreads();
-    if (threadIdx.x == 0) s_ticket = atomicAdd(&pctl->pad, 1u);
-    __syncthreads();
-    const uint32_t t = s_ticket;
-    if (t >= (uint32_t)B) return;
-    ImgDesc& d = desc[t];
-    if (d.status != DINO_IMG_OK || d.kind != kPngKind) continue;
-    InfDevIO io;
-    io.lane = threadIdx.x, io.nl = 64;
-    io.z = ws + d.ent_off, io.zcap = d.rst_off - d.ent_off, io.ring_base = -(int64_t)kInfRing * 2, io.ring = L.ring;
-    io.out = ws + d.plane_off, io.out_cap = d.rgb_off - d.plane_off;
-    io.win = L.win, io.lt = &L.lt, io.dt = &L.dt, io.lens = L.lens;
-    const int64_t want = png_inflated_bytes(d);
-    int st = DINO_IMG_CORRUPT;
-    if (want + 16 <= io.out_cap) {
-      Inflater<InfDevIO> inf(io, d.ent_len, want);
-      st = inf.run();
-    }
-    if (st != DINO_IMG_OK && threadIdx.x == 0) d.status = st;
-  }
-}
-
-// One wave per image reverses the row filters 64 rows at a time, lane r on row y0 + r one pixel
-// behind lane r - 1: at step t it reconstructs pixel x = t - r from its own previous pixel
-// (left), the pixel lane r - 1 reconstructed a step before (up) and the one before that
-// (up-left), all in registers (four channels packed in a word).  Lane 63's row goes to the
-// image's carry row for lane 0 of the next band.  Writes HWC RGB (png_to_rgb).  A filter byte
-// above 4 fails the image, as in ZipDecode.c.
-__global__ void __launch_bounds__(64) k_unfilter(ImgDesc* __restrict__ desc, uint8_t* __restrict__ ws) {
-  ImgDesc& d = desc[blockIdx.x];
-  if (d.status != DINO_IMG_OK || d.kind != kPngKind) return;
-  const int W = d.width, H = d.height, bpp = d.max_h, color = d.color, lane = threadIdx.x;
-  const int64_t stride = 1 + (int64_t)W * bpp;
-  const uint8_t* inf = ws + d.plane_off;
-  const uint8_t* pal = ws + d.htab_off;
-  uint32_t* carry = (uint32_t*)(ws + d.coef_off);  // W words
-  uint8_t* rgb = ws + d.rgb_off;
-  int bad = 0;
-  for (int y0 = 0; y0 < H; y0 += 64) {
-    const int y = y0 + lane;
-    const bool active = y < H;
-    const uint8_t* row = inf + (active ? y : 0) * stride + 1;
-    int f = active ? row[-1] : 0;
-    if (f > 4) bad = 1, f = 0;
-    uint32_t left = 0, upleft = 0, mine = 0;
-    for (int t = 0; t < W + 63; ++t) {
-      const int x = t - lane;
-      const bool in = active && x >= 0 && x < W;
-      uint32_t up = __shfl_up(mine, 1);
-      if (lane == 0) up = (y0 > 0 && in) ? carry[x] : 0u;
-      mine = 0;
-      if (in) {
-        uint8_t px[4] = {0, 0, 0, 0};
-        for (int c = 0; c < bpp; ++c) {
-          const int sh = 8 * c;
-          const int v = row[(int64_t)x * bpp + c] + png_predict(f, (left >> sh) & 255, (up >> sh) & 255, (upleft >> sh) & 255);
-          px[c] = (uint8_t)v;
-          mine |= (uint32_t)px[c] << sh;
-        }
-        png_to_rgb(color, px, pal, rgb + ((int64_t)y * W + x) * 3);
-        if (lane == 63) carry[x] = mine;
-      }
-      left = mine;
-      upleft = up;
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
-  if (__syncthreads_or(bad) && lane == 0) d.status = DINO_IMG_CORRUPT;
-}
-
-static const char* const kKernelNames[kKNumKernels] = {"k_parse", "k_plan", "k_destuff", "k_huff1", "k_idct",
-                                                       "k_color", "k_params", "k_vplan", "k_rcoeffs", "k_hresize",
-                                                       "k_final_global", "k_final_local", "k_vert_global",
-                                                       "k_vert_local", "k_dcscan", "k_htab", "k_hseg", "k_huff2",
-                                                       "k_huff3", "k_prog", "k_pwalk", "k_plscan",
-                                                       "k_papply", "k_png"};
-const char* g_failed_kernel = "";
-
-#define TIMED(tm, kid, s, launch)                          \
-  do {                                                     \
-    if (tm) (tm)->begin(kid, s);                           \
-    launch;                                                \
-    if (tm) (tm)->end(s);                                  \
-    if (g_sync_check) {                                    \
-      hipError_t se_ = hipStreamSynchronize(s);            \
-      if (se_ == hipSuccess) se_ = hipGetLastError();      \
-      if (se_ != hipSuccess) {                             \
-        g_failed_kernel = kKernelNames[kid];               \
-        fprintf(stderr, "[dino] %s failed: %s\n", kKernelNames[kid], hipGetErrorString(se_)); \
-        return se_;                                        \
-      }                                                    \
-    }                                                      \
-  } while (0)
-
-// Persistent grids of the segment kernels: as many workgroups as can be resident
-// on the device at once (occupancy query x CUs); items beyond them come in later turns.
-static int persistent_grid(const void* fn, int lds, int cus) {
-  int per = 4;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, kHuffThreads, lds) != hipSuccess || per < 1) per = 4;
-  return per * cus;
-}
-
-// Per-device launch geometry (called by dino_ctx_create with `device` current).
-hipError_t init_launch_geom(int device, LaunchGeom* g) {
-  int cus = 256;
-  hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-  if (e != hipSuccess) return e;
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_huff1), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               kHuffLdsBytes)) != hipSuccess)
-    return e;
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_huff3), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               kHuff3LdsBytes)) != hipSuccess)
-    return e;
-  g->grid_ds = 4 * cus;
-  g->grid3 = persistent_grid(reinterpret_cast<const void*>(&k_huff3), kHuff3LdsBytes, cus);
-  g->grid1 = persistent_grid(reinterpret_cast<const void*>(&k_huff1), kHuffLdsBytes, cus);
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hresize), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               kHresizeLds)) != hipSuccess)
-    return e;
-  g->grid_hr = persistent_grid(reinterpret_cast<const void*>(&k_hresize), kHresizeLds, cus);
-  // k_vfinal's tile and strip pass 64 KiB above S = 100
-  const int vf_lds = vfinal_strip_off<float>(kVFinalMaxS) + kVfStripBytes;
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vfinal<uint16_t>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               vf_lds)) != hipSuccess ||
-      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vfinal<float>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               vf_lds)) != hipSuccess ||
-      (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vfinal<uint8_t>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               vf_lds)) != hipSuccess)
-    return e;
-  // views up to this size take k_vfinal, larger ones k_vert + k_final (DINO_VFINAL_MAX_S: 0 sends
-  // every view through the two kernels, for parity tests and A/B runs)
-  const char* vm = getenv("DINO_VFINAL_MAX_S");
-  g->vfinal_max_s = vm ? min(max(atoi(vm), 0), kVFinalMaxS) : kVFinalMaxS;
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_plscan), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               kPLscanLds)) != hipSuccess)
-    return e;
-  // scan waves: one per CU by default.  A scan's serial decode runs on the CU's one scalar
-  // unit, which the CU's waves share: two scan waves on a CU each run at about half speed
-  // (DINO_PSCAN_PER_CU: waves per CU, measured in profiles/r03_prog_*).
-  const char* pc = getenv("DINO_PSCAN_PER_CU");
-  const int per_cu = pc && atoi(pc) > 0 ? atoi(pc) : 1;
-  g->grid_ps = per_cu * cus;
-  // lane scan waves: one ticket each (a 512-image pool of libjpeg-default files: 80); the rest exit
-  const char* ls = getenv("DINO_PLSCAN_WAVES");
-  g->grid_ls = ls && atoi(ls) > 0 ? atoi(ls) : 2 * cus;
-  // the scan waves' issue priority: 0 below the batch kernels (s_setprio 3, main_prio), 1 level
-  const char* sp = getenv("DINO_SCAN_PRIO");
-  g->scan_prio = sp ? atoi(sp) : 0;
-  // the lane decoder is opt-in (DINO_PROG_LANE=1): its throughput is higher but a scan's latency
-  // is ~3x a scan wave's, more than the side route's look-ahead covers
-  // inflate waves (PNG): four per CU fit its LDS (kInfLdsBytes each); DINO_INFLATE_WAVES sets the grid
-  const char* iw = getenv("DINO_INFLATE_WAVES");
-  g->grid_inf = iw && atoi(iw) > 0 ? atoi(iw) : 4 * cus;
-  const char* pl = getenv("DINO_PROG_LANE");
-  g->prog_lane = pl ? (atoi(pl) != 0) : 0;
-  return hipSuccess;
-}
-
-hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
-  const int B = a.batch;
-  if (B <= 0) return hipSuccess;
-  TIMED(tm, kKParse, s, (k_parse<<<B, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.max_dim, a.four_component,
-                                                  a.desc)));
-  // a context with dino_ctx_set_png on: PNG files get their descriptor before the plan
-  if (a.png) TIMED(tm, kKPng, s, (k_pnghead<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.max_dim, a.desc)));
-  // (k_plan<true> also sizes kind-4 images; without the option there is none and k_plan<false> is the code it was)
-  if (a.png) TIMED(tm, kKPlan, s, (k_plan<true><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
-  else TIMED(tm, kKPlan, s, (k_plan<false><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
-  const int grid_ds = a.geom.grid_ds, grid1 = a.geom.grid1, grid3 = a.geom.grid3;
-  TIMED(tm, kKDestuff, s, (k_destuff_count<<<grid_ds, kDestuffThreads, 0, s>>>(a.bytes, a.offsets, B, a.desc, a.ws)));
-  TIMED(tm, kKDestuff, s, (k_destuff_write<<<grid_ds, kDestuffThreads, 0, s>>>(a.bytes, a.offsets, B, a.desc, a.ws)));
-  TIMED(tm, kKHtab, s, (k_htab<<<B, kHuffThreads, 0, s>>>(a.bytes, a.offsets, a.desc, a.ws)));
-  // after k_htab's kind switch
-  TIMED(tm, kKPwalk, s, (k_pwalk<<<B, kPWalkThreads, 0, s>>>(a.bytes, a.offsets, a.lengths, a.desc, a.ws, a.pctl,
-                                                               a.geom.prog_lane)));
-  TIMED(tm, kKProg, s, (k_pscan<<<a.geom.grid_ps, kPScanThreads, 0, s>>>(a.bytes, a.offsets, a.lengths, a.desc, a.ws, a.pctl,
-                                                                             a.geom.scan_prio)));
-  if (a.geom.prog_lane) {  // the lane decoder (opt-in): k_pwalk registers no lane image otherwise
-    TIMED(tm, kKPlscan, s, (k_plscan<<<a.geom.grid_ls, 64, kPLscanLds, s>>>(a.desc, a.ws, a.pctl, a.geom.scan_prio)));
-    TIMED(tm, kKPapply, s, (k_papply<<<dim3(kPApplyWgs, B), 256, 0, s>>>(a.desc, a.ws, a.pctl)));
-  }
-  TIMED(tm, kKHseg, s, (k_hseg<<<1, 1024, 0, s>>>(a.desc, B)));
-  TIMED(tm, kKHuff1, s, (k_huff1<<<grid1, kHuffThreads, kHuffLdsBytes, s>>>(a.desc, B, a.ws)));
-  TIMED(tm, kKHuff2, s, (k_huff2<<<B, kHuff2Threads, 0, s>>>(a.desc, a.ws)));
-  TIMED(tm, kKHuff3, s, (k_huff3<<<grid3, kHuffThreads, kHuff3LdsBytes, s>>>(a.desc, B, a.ws)));
-  TIMED(tm, kKDcscan, s, (k_dcscan<<<B, kDcScanThreads, 0, s>>>(a.desc, a.ws)));
-  TIMED(tm, kKIdct, s, (k_idct<<<dim3(kIdctWgs, B), 256, 0, s>>>(a.desc, a.ws)));
-  if (a.four_component) TIMED(tm, kKIdct, s, (k_idct4<<<dim3(kIdctWgs, B), 256, 0, s>>>(a.desc, a.ws)));
-  TIMED(tm, kKColor, s, (k_color<<<dim3(kColorWgs, B), 256, 0, s>>>(a.bytes, a.offsets, a.desc, a.ws)));
-  if (a.four_component) TIMED(tm, kKColor, s, (k_color4<<<dim3(kColorWgs, B), 256, 0, s>>>(a.desc, a.ws)));
-  if (a.png) {  // PNG images (kind 4): no other context has one
-    TIMED(tm, kKPng, s, (k_pngwalk<<<B, kPngWalkThreads, 0, s>>>(a.bytes, a.offsets, a.lengths, a.desc, a.ws, a.pctl)));
-    TIMED(tm, kKPng, s, (k_inflate<<<min(B, a.geom.grid_inf), 64, 0, s>>>(a.desc, a.ws, a.pctl, B)));
-    TIMED(tm, kKPng, s, (k_unfilter<<<B, 64, 0, s>>>(a.desc, a.ws)));
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_params(const ImgDesc* desc, int batch, const dino_aug_config& cfg, uint64_t seed,
-                         uint64_t batch_index, dino_view_params* out, hipStream_t s, KernelTimer* tm) {
-  const int n = batch * (cfg.n_global + cfg.n_local);
-  if (n <= 0) return hipSuccess;
-  TIMED(tm, kKParams, s, (k_params<<<(n + 63) / 64, 64, 0, s>>>(desc, batch, cfg, seed, batch_index, out)));
-  return hipGetLastError();
-}
-
-template <typename OutT>
-static hipError_t launch_augment_class(const AugmentArgs& a, int v0, int nvc, int S, hipStream_t s, KernelTimer* tm) {
-  const int B = a.batch, nv = a.cfg.n_global + a.cfg.n_local;
-  if (nvc <= 0) return hipSuccess;
-  const int kfin = v0 == 0 ? kKFinalGlobal : kKFinalLocal;
-  const int kvert = v0 == 0 ? kKVertGlobal : kKVertLocal;
-  const int rc_threads = S < 256 ? (S + 63) / 64 * 64 : 256;  // one lane per output column
-  TIMED(tm, kKRcoeffs, s, (k_rcoeffs<<<dim3(nvc, B), rc_threads, 0, s>>>(a.desc, a.params, a.plan, nv, v0, a.filter, a.ws, a.aws)));
-  TIMED(tm, kKHresize, s,
-        (k_hresize<<<a.grid_hr, 256, kHresizeLds, s>>>(a.desc, a.params, a.plan, nv, v0, nvc, B, a.ws, a.aws)));
-  if (S <= a.vfinal_max_s) {  // small views: vertical pass and epilogue fused, the view stays in LDS
-    const int lds = vfinal_strip_off<OutT>(S) + kVfStripBytes;
-    TIMED(tm, kfin, s,
-          (k_vfinal<OutT><<<dim3(nvc, B), kVFinalThreads, lds, s>>>(a.desc, a.params, a.plan, nv, v0, a.ws, a.aws, a.views, a.cfg,
-                                                         S, a.norm)));
-    return hipGetLastError();
-  }
-  TIMED(tm, kvert, s,
-        (k_vert<<<dim3((S + vert_rows(S) - 1) / vert_rows(S), nvc, B), 256, 0, s>>>(a.desc, a.params, a.plan, nv, v0, B,
-                                                                             a.ws, a.aws, a.gcrop, a.cfg, S)));
-  const int lds = (int)sizeof(FinalLds) + final_tile_bytes(S) + 3 * 256 * (int)sizeof(OutT);
-  TIMED(tm, kfin, s,
-        (k_final<OutT><<<dim3((S + final_rows(S) - 1) / final_rows(S), nvc, B), 256, lds, s>>>(
-            a.desc, a.params, a.plan, nv, v0, B, a.gcrop, a.views, a.cfg, S, a.norm)));
-  return hipGetLastError();
-}
-
-template <typename OutT>
-static hipError_t launch_augment_t(const AugmentArgs& a, hipStream_t s, KernelTimer* tm) {
-  hipError_t e = launch_augment_class<OutT>(a, 0, a.cfg.n_global, a.cfg.global_size, s, tm);
-  if (e != hipSuccess) return e;
-  return launch_augment_class<OutT>(a, a.cfg.n_global, a.cfg.n_local, a.cfg.local_size, s, tm);
-}
-
-hipError_t launch_augment(const AugmentArgs& a, hipStream_t s, KernelTimer* tm) {
-  const int B = a.batch, nv = a.cfg.n_global + a.cfg.n_local;
-  if (B <= 0 || nv <= 0) return hipSuccess;
-  TIMED(tm, kKVplan, s, (k_vsizes<<<(B * nv + 255) / 256, 256, 0, s>>>(a.desc, a.params, B, nv, a.cfg.n_global,
-                                                                       a.cfg.global_size, a.cfg.local_size, a.filter, a.plan)));
-  TIMED(tm, kKVplan, s, (k_vplan<<<1, 1024, 0, s>>>(a.desc, a.params, B, nv, a.cfg.n_global, a.cfg.global_size,
-                                                     a.cfg.local_size, a.aws_size, a.plan)));
-  switch (a.cfg.out_dtype) {
-    case DINO_OUT_FP32:
-      return launch_augment_t<float>(a, s, tm);
-    case DINO_OUT_FP8_E4M3:
-      return launch_augment_t<uint8_t>(a, s, tm);
-    default:
-      return launch_augment_t<uint16_t>(a, s, tm);
-  }
-}
-
-hipError_t launch_info(const ImgDesc* desc, int batch, int32_t* info, hipStream_t s) {
-  if (batch <= 0) return hipSuccess;
-  k_info<<<(batch + 63) / 64, 64, 0, s>>>(desc, batch, info);
-  return hipGetLastError();
-}
-
-// The per-pixel colour operators over all 2^24 inputs (index = a << 16 | b << 8 | c):
-// op 0 RGB -> HSV, op 1 HSV -> RGB, op 2 hue_shift by `param` (the ColorJitter hue op);
-// out[3 * index + k].  For the exhaustive device-side checks against Pillow.
-__global__ void __launch_bounds__(256) k_pixel_ops(int op, int param, uint8_t* __restrict__ out) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  int x = (idx >> 16) & 255, y = (idx >> 8) & 255, z = idx & 255;
-  if (op == 0) {
-    int h, sv, v;
-    rgb_to_hsv(x, y, z, &h, &sv, &v);
-    x = h, y = sv, z = v;
-  } else if (op == 1) {
-    hsv_to_rgb(x, y, z, &x, &y, &z);
-  } else {
-    hue_shift(x, y, z, param);
-  }
-  out[3 * (int64_t)idx] = (uint8_t)x;
-  out[3 * (int64_t)idx + 1] = (uint8_t)y;
-  out[3 * (int64_t)idx + 2] = (uint8_t)z;
-}
-
-hipError_t launch_pixel_ops(int op, int param, uint8_t* out, hipStream_t s) {
-  k_pixel_ops<<<(1 << 24) / 256, 256, 0, s>>>(op, param, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_copy_rgb(const ImgDesc* desc, int idx, const uint8_t* ws, uint8_t* dst, hipStream_t s) {
-  k_copy_rgb<<<256, 256, 0, s>>>(desc, idx, ws, dst);
-  return hipGetLastError();
-}
-
-hipError_t launch_copy_rgb_packed(const ImgDesc* desc, int B, int n, const int32_t* idx, const int64_t* off,
-                                  const uint8_t* ws, uint8_t* base, int header, hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  k_copy_rgb_packed<<<dim3(16, n), 256, 0, s>>>(desc, B, idx, off, ws, base, header);
-  return hipGetLastError();
-}
-
-hipError_t launch_masks(int H, int W, int target, int minp, int maxp, double la0, double la1, int n, uint32_t* py,
-                        uint32_t* np, uint8_t* out, hipStream_t s) {
-  MaskParams mp{H, W, target, minp, maxp, la0, la1};
-  if ((int64_t)H * W > kMaskLdsMaxPatches) return hipErrorInvalidValue;
-  k_masks<<<1, 64, 5 * H * W + 16, s>>>(mp, n, py, np, out);
-  return hipGetLastError();
-}
-
-#ifdef DINO_HUFF_PHASES
-hipError_t copy_huff_phases(uint64_t* host, int64_t n_items) {
-  hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) return e;
-  const int64_t n = n_items < kPhaseItems ? n_items : kPhaseItems;
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_huff_phase), sizeof(uint64_t) * 5 * n);
-}
-#endif
-
-hipError_t launch_bf16_to_fp8(const uint16_t* in, uint8_t* out, int64_t n, hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  k_bf16_to_fp8<<<(unsigned)blocks, 256, 0, s>>>(in, out, n);
-  return hipGetLastError();
-}
+#include "kernels_decode_only.inc"
+#include "kernels_small.inc"
+#include "kernels_timer.inc"
+#include "kernels_png.inc"
+#include "kernels_launch.inc"
 
 }  // namespace dino
