@@ -78,6 +78,8 @@ def load() -> ctypes.CDLL:
         "dino_feed_last_error": (ctypes.c_char_p, []),
         "dino_host_register": (i32, [vp, i64]),
         "dino_host_unregister": (i32, [vp]),
+        "dino_host_alloc": (i32, [i64, ctypes.POINTER(vp)]),
+        "dino_host_free": (i32, [vp]),
         "dino_copy_h2d": (i32, [vp, vp, i64, vp]),
         "dino_stream_create": (i32, [i32, i32, ctypes.POINTER(vp)]),
         "dino_stream_destroy": (i32, [vp]),
@@ -133,7 +135,8 @@ def exported_symbols() -> list[str]:
             "dino_ctx_set_prog_decoder", "dino_copy_rgb_packed", "dino_tar_index", "dino_tar_index_fd", "dino_tar_last_error", "dino_gather", "dino_set_norm", "dino_batch_info",
             "dino_probe", "dino_reserve", "dino_workspace_sizes", "dino_masks_host", "dino_resize_batch",
             "dino_augment_need", "dino_decode_spans", "dino_run_batch_spans", "dino_probe_spans",
-            "dino_host_register", "dino_host_unregister", "dino_copy_h2d", "dino_gather_probe",
+            "dino_host_register", "dino_host_unregister", "dino_host_alloc", "dino_host_free", "dino_copy_h2d",
+            "dino_gather_probe",
             "dino_feed_create", "dino_feed_destroy", "dino_feed_push", "dino_feed_end_epoch", "dino_feed_set_cfg",
             "dino_feed_set_shard_wait", "dino_feed_set_shuffle", "dino_feed_set_epoch",
             "dino_feed_next", "dino_feed_copy", "dino_feed_release", "dino_feed_reset", "dino_feed_stats",

@@ -495,8 +495,27 @@ int dino_host_register(void* host, int64_t nbytes) {
   if (e != hipSuccess) {
     (void)hipGetLastError();
     e = hipHostRegister(host, (size_t)nbytes, hipHostRegisterDefault);
+    if (e != hipSuccess) (void)hipGetLastError();  // reported here, not by the caller's next launch
   }
   return e == hipSuccess ? DINO_OK : hip_fail(e, "dino_host_register");
+}
+
+int dino_host_alloc(int64_t nbytes, void** host) {
+  if (!host || nbytes <= 0) return fail(DINO_EINVAL, "dino_host_alloc: bad arguments%s%lld");
+  *host = nullptr;
+  hipError_t e = hipHostMalloc(host, (size_t)nbytes, hipHostMallocDefault);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    *host = nullptr;
+    return hip_fail(e, "dino_host_alloc");
+  }
+  return DINO_OK;
+}
+
+int dino_host_free(void* host) {
+  if (!host) return DINO_OK;
+  hipError_t e = hipHostFree(host);
+  return e == hipSuccess ? DINO_OK : hip_fail(e, "dino_host_free");
 }
 
 int dino_host_unregister(void* host) {

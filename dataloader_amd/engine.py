@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import warnings
 
 import numpy as np
 import torch
@@ -49,7 +50,16 @@ def pack_jpegs(jpegs, pin: bool = True) -> tuple[torch.Tensor, torch.Tensor]:
     offsets = np.zeros(len(jpegs) + 1, dtype=np.int64)
     np.cumsum(lens, out=offsets[1:])
     total = int(offsets[-1])
-    buf = torch.empty(max(total, 1) + 16, dtype=torch.uint8, pin_memory=pin)
+    try:
+        buf = torch.empty(max(total, 1) + 16, dtype=torch.uint8, pin_memory=pin)
+    except RuntimeError as e:
+        if not pin or not torch.cuda.is_available():
+            raise
+        # a host may cap page-locked memory (a virtual machine's share of it) below a large
+        # set: pageable memory holds the same bytes, only its copies to the device are staged
+        warnings.warn(f"pack_jpegs: no page-locked buffer of {total + 16} bytes ({str(e).splitlines()[0]}); "
+                      "packing into pageable memory", RuntimeWarning, stacklevel=2)
+        buf = torch.empty(max(total, 1) + 16, dtype=torch.uint8)
     view = buf.numpy()
     for j, o, n in zip(jpegs, offsets[:-1], lens):
         view[o:o + n] = np.frombuffer(j, dtype=np.uint8) if isinstance(j, (bytes, bytearray, memoryview)) else j

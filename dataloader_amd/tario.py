@@ -562,7 +562,11 @@ class ShardBatchFeeder:
       pipeline DMAs the shard ranges straight to HBM (no host copy) and decodes
       with the spans ABI; ``retire(batch, event)`` hands back the event after which
       the copies have read the ranges, and a consumed shard is unregistered once
-      every batch taken from it has retired;
+      every batch taken from it has retired.  Where the runtime cannot page-lock a
+      mapping (``hipHostRegister`` fails, as on some virtual machines), each shard is
+      copied once, on the worker thread, into page-locked memory of the runtime's own
+      and the batch's ranges point into that copy, freed by the same rule
+      (``page_lock`` tells which: "register" or "copy");
     * ``next_spans()`` / ``next_into(dst)``: (address, length) pairs, packed by
       ``dino_gather`` into a pinned buffer (batches the pipeline must re-pack, e.g.
       with Pillow hand-overs)."""
@@ -583,8 +587,11 @@ class ShardBatchFeeder:
         self._pool = ThreadPoolExecutor(max_workers=max(1, self._lookahead), thread_name_prefix="shard-index") \
             if self._lookahead else None
         self._futs: dict[int, Any] = {}
-        self._register = bool(register)
-        self.register_error: str | None = None
+        # how shards are page-locked: "register" (the mapping itself), "copy" (a page-locked
+        # copy, once the runtime has refused to register a mapping), None (not at all)
+        self.page_lock: str | None = "register" if register else None
+        self._register_refused = ""
+        self.register_error: str | None = None  # why shards are not page-locked although asked for
         self._reg_lock = threading.Lock()
         # shard index -> {"addr", "handed", "retired", "events", "consumed"} of page-locked shards
         self._reg: dict[int, dict] = {}
@@ -597,7 +604,7 @@ class ShardBatchFeeder:
         arr = self._cache.get_array(self._paths[k])
         prefault(arr)
         idx = index_tar(arr)
-        if self._register and arr.size:
+        if self.page_lock and arr.size:
             with self._reg_lock:
                 ent = self._reg.get(k)
                 if ent is not None:          # still locked from an earlier epoch
@@ -606,16 +613,33 @@ class ShardBatchFeeder:
                 else:
                     need = True
             if need:
-                rc = _lib.load().dino_host_register(ctypes.c_void_p(arr.ctypes.data), arr.nbytes)
-                if rc == 0:
+                addr, copy = self._page_locked(arr)
+                if addr:
                     with self._reg_lock:
-                        self._reg[k] = {"addr": arr.ctypes.data, "handed": 0, "retired": 0, "events": [],
+                        self._reg[k] = {"addr": addr, "copy": copy, "handed": 0, "retired": 0, "events": [],
                                         "consumed": False}
-                else:  # no GPU runtime / the mapping cannot be locked: the gather path serves
-                    self._register = False
-                    self.register_error = _lib.load().dino_last_error().decode(errors="replace")
         self.index_seconds += time.perf_counter() - t0
         return arr, idx
+
+    def _page_locked(self, arr: np.ndarray) -> tuple[int, bool]:
+        """(address, is a copy) of the shard's bytes in page-locked memory, (0, False) when
+        there is none.  The mapping itself where the runtime registers it; where it does not
+        (some virtual machines), from then on a copy in page-locked memory of the runtime's."""
+        lib = _lib.load()
+        if self.page_lock == "register":
+            if lib.dino_host_register(ctypes.c_void_p(arr.ctypes.data), arr.nbytes) == 0:
+                return arr.ctypes.data, False
+            self._register_refused = lib.dino_last_error().decode(errors="replace")
+            self.page_lock = "copy"
+        if self.page_lock == "copy":
+            host = ctypes.c_void_p()
+            if lib.dino_host_alloc(arr.nbytes, ctypes.byref(host)) == 0:
+                ctypes.memmove(host, ctypes.c_void_p(arr.ctypes.data), arr.nbytes)
+                return host.value, True
+            # no GPU runtime, or no page-locked memory left: the gather path serves
+            self.register_error = f"{self._register_refused}; {lib.dino_last_error().decode(errors='replace')}"
+            self.page_lock = None
+        return 0, False
 
     def _open(self, k: int) -> tuple[np.ndarray, TarIndex]:
         import time
@@ -680,17 +704,19 @@ class ShardBatchFeeder:
             io, il = rows["img_off"], rows["img_len"]
             lo, hi = int(io[0]), int(io[-1] + il[-1])
             n = len(rows)
-            ptrs[i:i + n] = arr.ctypes.data + io
-            lens[i:i + n] = il
-            offs[i:i + n] = pos + (io - lo)
-            parts.append((arr.ctypes.data + lo, hi - lo))
-            shards.append(k)
             with self._reg_lock:
                 ent = self._reg.get(k)
                 if ent is None:
                     registered = False
-                else:
+                    base = arr.ctypes.data
+                else:  # a page-locked copy lives until this batch retires
                     ent["handed"] += 1
+                    base = ent["addr"]
+            ptrs[i:i + n] = base + io
+            lens[i:i + n] = il
+            offs[i:i + n] = pos + (io - lo)
+            parts.append((base + lo, hi - lo))
+            shards.append(k)
             pos += hi - lo
             i += n
         offs[self._B] = pos
@@ -731,7 +757,10 @@ class ShardBatchFeeder:
                 done.append(k)
             for k in done:
                 ent = self._reg.pop(k)
-                _lib.load().dino_host_unregister(ctypes.c_void_p(ent["addr"]))
+                if ent["copy"]:
+                    _lib.load().dino_host_free(ctypes.c_void_p(ent["addr"]))
+                else:
+                    _lib.load().dino_host_unregister(ctypes.c_void_p(ent["addr"]))
 
     def next_into(self, dst) -> np.ndarray:
         return gather(self.next_spans(), dst, self.nthreads)

@@ -50,7 +50,8 @@
  *    and dino_resample_coeffs_host; dino_ctx_set_four_component (four-component Adobe CMYK /
  *    YCCK JPEGs decoded on the device, off by default) and kind 3 in the probes' info;
  *    dino_ctx_set_png (PNG files decoded on the device, off by default), kinds 4 and 5 in the
- *    probes' info, dino_kernel_times id 23, dino_debug_region 10 and 11.
+ *    probes' info, dino_kernel_times id 23, dino_debug_region 10 and 11; dino_host_alloc /
+ *    dino_host_free (page-locked memory for hosts where a mapping cannot be registered).
  */
 #ifndef DINO_INGEST_H
 #define DINO_INGEST_H
@@ -275,6 +276,11 @@ int dino_gather_probe(const uint64_t* src_ptrs, const int64_t* lens, int32_t n, 
  * after every copy from the range has retired. */
 int dino_host_register(void* host, int64_t nbytes);
 int dino_host_unregister(void* host);
+/* Page-locked host memory of the runtime's own (hipHostMalloc), for where an existing
+ * range cannot be registered: the caller copies the range in once and DMAs from the copy.
+ * Free only after every copy from it has retired. */
+int dino_host_alloc(int64_t nbytes, void** host);
+int dino_host_free(void* host);
 /* Asynchronous host -> device copy on `stream` (a DMA when host lies in registered or
  * pinned memory). */
 int dino_copy_h2d(void* d_dst, const void* host_src, int64_t nbytes, void* stream);

@@ -296,6 +296,96 @@ def test_shard_spans_feed_dma_matches_packed_feed(gpu_device, tmp_path):
     cache.close(remove=True)
 
 
+def test_shard_spans_from_a_page_locked_copy(gpu_device, tmp_path):
+    """A feeder whose runtime does not register mappings (``page_lock`` "copy", what a refused
+    hipHostRegister switches to): every batch is page-locked and lies outside the mapping, its
+    ranges DMA'd to HBM and cut at offsets/lens are the shard's images across shard boundaries
+    and a second epoch, and a shard's copy is freed once it is consumed and its batches have
+    retired."""
+    import ctypes
+    import io as _io
+    import tarfile
+
+    from dataloader_amd import _lib
+    from dataloader_amd.tario import ShardBatchFeeder, ShmShardCache
+    rng = np.random.default_rng(57)
+    samples = [rng.integers(0, 256, size=int(n), dtype=np.uint8).tobytes() for n in rng.integers(700, 5000, size=13)]
+    shards = []
+    for s0 in (0, 5, 10):  # 5, 5, 3 samples: batches of 4 straddle shards
+        buf = _io.BytesIO()
+        with tarfile.open(fileobj=buf, mode="w") as tf:
+            for i in range(s0, min(13, s0 + 5)):
+                ti = tarfile.TarInfo(f"sample_{i:06d}.jpg")
+                ti.size = len(samples[i])
+                tf.addfile(ti, _io.BytesIO(samples[i]))
+        shards.append(buf.getvalue())
+    cache = ShmShardCache(job_id="spans_copy", base_dir=tmp_path)
+    paths = [f"/d/shard-{k}.tar" for k in range(len(shards))]
+    for p, t in zip(paths, shards):
+        cache.put(p, t)
+    maps = [cache.get_array(p) for p in paths]
+    feeder = ShardBatchFeeder(cache, paths, 4, nthreads=2, register=True)
+    feeder.page_lock = "copy"
+    lib = _lib.load()
+    stream = torch.cuda.current_stream(gpu_device)
+    for _epoch in range(2):
+        got = []
+        while True:
+            try:
+                bs = feeder.next_batch_spans()
+            except StopIteration:
+                break
+            assert bs.registered
+            for addr, n in bs.parts:
+                assert not any(m.ctypes.data <= addr < m.ctypes.data + m.nbytes for m in maps)
+            d = torch.empty(int(bs.offsets[-1]), dtype=torch.uint8, device=gpu_device)
+            pos = 0
+            for addr, n in bs.parts:
+                _lib.check(lib.dino_copy_h2d(ctypes.c_void_p(d.data_ptr() + pos), ctypes.c_void_p(addr), n,
+                                             ctypes.c_void_p(stream.cuda_stream)), "dino_copy_h2d")
+                pos += n
+            ev = torch.cuda.Event()
+            ev.record(stream)
+            feeder.retire(bs, ev)
+            flat = d.cpu().numpy().tobytes()
+            got += [flat[bs.offsets[i]:bs.offsets[i] + bs.lens[i]] for i in range(4)]
+        assert got == samples[:12]
+        assert 0 not in feeder._reg, feeder._reg  # consumed, retired and copied long ago
+        feeder.reset()
+    feeder.close()
+    assert feeder.page_lock == "copy" and feeder.register_error is None and not feeder._reg
+    cache.close(remove=True)
+
+
+def test_pack_jpegs_packs_pageable_when_no_page_locked_buffer_is_granted(gpu_device, monkeypatch):
+    """A host that refuses the page-locked buffer (a capped virtual machine, a very large set):
+    pack_jpegs says so in a warning and packs the same bytes and offsets into pageable memory;
+    an allocation that fails without pinning still raises."""
+    rng = np.random.default_rng(58)
+    jpegs = [rng.integers(0, 256, size=int(n), dtype=np.uint8).tobytes() for n in (1, 700, 33)]
+    ref, ref_off = pack_jpegs(jpegs, pin=True)
+    assert ref.is_pinned()
+    real = torch.empty
+
+    def refusing(*a, **kw):
+        if kw.get("pin_memory"):
+            raise RuntimeError("HIP error: out of memory")  # torch.AcceleratorError is a RuntimeError
+        return real(*a, **kw)
+
+    monkeypatch.setattr(torch, "empty", refusing)
+    with pytest.warns(RuntimeWarning, match="pageable"):
+        got, off = pack_jpegs(jpegs, pin=True)
+    assert not got.is_pinned() and torch.equal(got[:734], ref[:734]) and torch.equal(off, ref_off)
+    assert torch.equal(got.to(gpu_device)[:734].cpu(), ref[:734])
+
+    def failing(*a, **kw):
+        raise RuntimeError("no memory at all")
+
+    monkeypatch.setattr(torch, "empty", failing)
+    with pytest.raises(RuntimeError, match="no memory at all"):
+        pack_jpegs(jpegs, pin=False)
+
+
 def test_output_views_reused_only_after_the_caller_drops_them(gpu_device):
     """A slot refills its previous output tensors only when the caller no longer references
     them (DALI's iterator contract); batches the caller keeps are never overwritten."""
