@@ -122,7 +122,7 @@ class MI355XBackend:
     def __init__(self, max_image_dim: int = 0, workspace_bytes: int = 0, max_in_flight: int = 3,
                  hbm_fraction: float = 0.15, host_workers: int | None = None, multiscan_route: str = "side",
                  side_ahead: int | None = None, resample_filter: str | None = None,
-                 four_component: str = "host", png: str = "off") -> None:
+                 four_component: str = "host", png: str = "off", jpeg_draft: int = 0) -> None:
         # Pillow filter of every resize: None = bicubic everywhere (CPUBackend parity, which
         # ignores EvalAugSpec.interpolation too); a filter's name applies to every recipe;
         # "spec" honours EvalAugSpec.interpolation as the reference's GPU peer does
@@ -146,6 +146,15 @@ class MI355XBackend:
         if png not in ("off", "host", "device"):
             raise ValueError(f"png must be 'off', 'host' or 'device', not {png!r}")
         self._png = png
+        # reduced-size JPEG decode, off at 0: N > 0 decodes every JPEG as Pillow does after
+        # im.draft("RGB", (N, N)) (1/2, 1/4 or 1/8 of the coded size where both sides stay >= N;
+        # fallback.draft_scale), on the device (libjpeg's reduced inverse DCTs) and in every
+        # hand-over.  Not CPUBackend's pixels: a loader that crops to N or less no longer makes,
+        # stores and reads the full-size image.  Four-component frames do not scale on the device
+        from .fallback import check_draft
+        self._jpeg_draft = check_draft(jpeg_draft)
+        if self._jpeg_draft and four_component == "device":
+            raise ValueError("jpeg_draft > 0 needs four_component='host': four-component frames do not scale on the device")
         self._max_image_dim = max_image_dim
         self._workspace_bytes = workspace_bytes
         self._max_in_flight = max(1, int(max_in_flight))
@@ -255,7 +264,8 @@ class MI355XBackend:
             return MI355XUserAugPipeline(source, aug_spec, getattr(source, "_batch_size", 1),
                                          out_dtype=pipeline_cfg.output_dtype, device=pipeline_cfg.device_id,
                                          max_image_dim=self._max_image_dim, workspace_bytes=self._workspace_bytes,
-                                         norm=norm, resample_filter=self.spec_filter(aug_spec), png=self._png)
+                                         norm=norm, resample_filter=self.spec_filter(aug_spec), png=self._png,
+                                         jpeg_draft=self._jpeg_draft)
         if _is_dinov2_spec(aug_spec):
             aug_cfg = aug_spec.aug_cfg
             names = None
@@ -300,6 +310,7 @@ class MI355XBackend:
             resample_filter=self.spec_filter(aug_spec),
             four_component=self._four_component,
             png=self._png,
+            jpeg_draft=self._jpeg_draft,
         )
 
     def build_pipeline_iterator(self, pipeline: Any, aug_spec: Any, output_map: list[str],

@@ -65,6 +65,7 @@ struct dino_ctx {
   int32_t filter = kBicubic;  // dino_ctx_set_resample_filter: read at each augment / resize launch
   int32_t four_component = 0; // dino_ctx_set_four_component: read at each decode launch
   int32_t png = 0;            // dino_ctx_set_png: read at each decode launch
+  int32_t draft = 0;          // dino_ctx_set_draft: read at each decode launch
   KernelTimer* timer = nullptr;
   KernelTimer* tm() { return timer && timer->enabled ? timer : nullptr; }
 };
@@ -149,7 +150,7 @@ int dino_decode_spans(dino_ctx* c, const uint8_t* d_bytes, const int64_t* d_offs
     return fail(DINO_EINVAL, "dino_decode: batch %s%lld exceeds ctx max_batch", "", batch);
   hipStream_t s = (hipStream_t)stream;
   DecodeArgs a{d_bytes, d_offsets, d_lengths, d_raw_mask, batch, c->lim.max_image_dim, c->d_desc, c->d_ws,
-               c->ws_size, c->geom, c->d_pctl, c->four_component, c->png};
+               c->ws_size, c->geom, c->d_pctl, c->four_component, c->png, c->draft};
   hipError_t e = launch_decode(a, s, c->tm());
   if (e != hipSuccess) return hip_fail(e, "dino_decode");
   if (d_info && (e = launch_info(c->d_desc, batch, d_info, s)) != hipSuccess) return hip_fail(e, "dino_decode(info)");
@@ -582,6 +583,13 @@ int dino_ctx_set_four_component(dino_ctx* c, int32_t on) {
 int dino_ctx_set_png(dino_ctx* c, int32_t on) {
   if (!c) return fail(DINO_EINVAL, "dino_ctx_set_png: null ctx%s%lld");
   c->png = on != 0;  // read at each launch (launch_decode)
+  return DINO_OK;
+}
+
+int dino_ctx_set_draft(dino_ctx* c, int32_t n) {
+  if (!c) return fail(DINO_EINVAL, "dino_ctx_set_draft: null ctx%s%lld");
+  if (n < 0) return fail(DINO_EINVAL, "dino_ctx_set_draft: negative size%s %lld", "", (long long)n);
+  c->draft = n;  // read at each launch (launch_decode)
   return DINO_OK;
 }
 

@@ -53,7 +53,7 @@ struct ImgDesc {
   int64_t ent_off, rst_off, plane_off, rgb_off;
   int64_t coef_off;        // sparse AC entries (u32, 64 per block of capacity; k_huffman SparseSink)
   int64_t cps_off;         // k_huffman checkpoints (speculative decode), kHuffThreads x kHuffCheckpoints
-  int64_t reserved0;
+  int32_t full_w, full_h;  // draft_shift != 0: the coded width and height (k_draft; width / height are the scaled ones)
   int64_t binfo_off;       // uint2 per block (decode order): first sparse entry, (int16 DC << 16) | entry count
   int64_t coef_bytes;      // dense int16 coefficient bytes (host emulator layout)
   int64_t htab_off;        // Huffman decoder tables (6 x HuffTable), built once per image by k_htab
@@ -65,7 +65,7 @@ struct ImgDesc {
   int32_t h_item_base;     // first work item of the image in the batch (k_hseg)
   int32_t ds_items;        // destuff work items (32 KiB parts of the scan, k_plan)
   int32_t ds_item_base;    // first destuff work item of the image in the batch (k_plan)
-  int32_t pad2;
+  int32_t draft_shift;     // reduced-size decode: output is 1 / (1 << shift) of the coded size (0 unless k_draft set it)
   int64_t dspart_off;      // per-part counts of k_destuff_count (16 bytes per part)
   // filled by k_destuff
   int32_t ent_len;         // destuffed entropy bytes

@@ -98,4 +98,105 @@ DHD void idct_block(const int16_t* coef, const uint16_t* q, uint8_t* out, int64_
   for (int r = 0; r < 8; ++r) idct_pass2(ws + r * 8, out + r * pitch);
 }
 
+// ---------------------------------------------------------------------------
+// Reduced-size inverse DCTs (libjpeg jidctred.c: jpeg_idct_4x4, jpeg_idct_2x2, jpeg_idct_1x1),
+// what a decode at 1/2, 1/4 and 1/8 size runs per block (Pillow's Image.draft).  Same
+// CONST_BITS / PASS1_BITS as above.  Both passes of a size are one butterfly with another
+// descale; jidctred.c's zero-AC shortcuts give the butterfly's own result (DC << 14 descaled by
+// 12 is DC << 2; w << 14 descaled by 19 is w descaled by 5) and are left out.  The sums are
+// int32 with wrap-around: exact for the coefficients of valid 8-bit data, which is where the
+// library's SIMD forms (jidctred-sse2.asm) agree with the C text as well.
+// ---------------------------------------------------------------------------
+constexpr int32_t R0_211 = 1730, R0_509 = 4176, R0_601 = 4926, R0_720 = 5906, R0_765 = 6270, R0_850 = 6967,
+                  R0_899 = 7373, R1_061 = 8697, R1_272 = 10426, R1_451 = 11893, R1_847 = 15137, R2_172 = 17799,
+                  R2_562 = 20995, R3_624 = 29692;
+
+DHD int32_t mul_w32(int32_t a, int32_t b) { return (int32_t)((uint32_t)a * (uint32_t)b); }
+DHD uint8_t range_limit8(int32_t x) { return (uint8_t)clamp_i32(x + 128, 0, 255); }
+
+// jpeg_idct_4x4, one column or row: inputs 0-3 and 5-7 (4 is never read) -> o[0..3] before
+// the descale (jidctred.c "Even part" / "Odd part" of either pass).
+DHD void idct4_core(const int32_t* in, int32_t* o) {
+  const int32_t tmp0 = mul_w32(in[0], 1 << (kConstBits + 1));
+  const int32_t tmp2 = add_w32(mul_w32(in[2], R1_847), mul_w32(in[6], -R0_765));
+  const int32_t t10 = add_w32(tmp0, tmp2), t12 = sub_w32(tmp0, tmp2);
+  const int32_t z1 = in[7], z2 = in[5], z3 = in[3], z4 = in[1];
+  const int32_t u0 = add_w32(add_w32(mul_w32(z1, -R0_211), mul_w32(z2, R1_451)),
+                             add_w32(mul_w32(z3, -R2_172), mul_w32(z4, R1_061)));
+  const int32_t u2 = add_w32(add_w32(mul_w32(z1, -R0_509), mul_w32(z2, -R0_601)),
+                             add_w32(mul_w32(z3, R0_899), mul_w32(z4, R2_562)));
+  o[0] = add_w32(t10, u2);
+  o[3] = sub_w32(t10, u2);
+  o[1] = add_w32(t12, u0);
+  o[2] = sub_w32(t12, u0);
+}
+// Pass 1 of column != 4: raw coefficients c[0..7] (rows) and quant values q -> workspace rows 0-3.
+DHD void idct4_pass1(const int32_t* c, const int32_t* q, int32_t* w) {
+  int32_t in[8], o[4];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) in[r] = mul_w32(c[r], q[r]);
+  idct4_core(in, o);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) w[r] = simd_descale(o[r], kConstBits - kPass1Bits + 1);
+}
+// Pass 2 of one workspace row (columns 0-3, 5-7) -> 4 samples.
+DHD void idct4_pass2(const int32_t* w, uint8_t* out) {
+  int32_t o[4];
+  idct4_core(w, o);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out[k] = range_limit8(simd_descale(o[k], kConstBits + kPass1Bits + 3 + 1));
+}
+
+// jpeg_idct_2x2, one column or row: inputs 0, 1, 3, 5, 7 -> o[0..1] before the descale.
+DHD void idct2_core(const int32_t* in, int32_t* o) {
+  const int32_t t10 = mul_w32(in[0], 1 << (kConstBits + 2));
+  const int32_t t0 = add_w32(add_w32(mul_w32(in[7], -R0_720), mul_w32(in[5], R0_850)),
+                             add_w32(mul_w32(in[3], -R1_272), mul_w32(in[1], R3_624)));
+  o[0] = add_w32(t10, t0);
+  o[1] = sub_w32(t10, t0);
+}
+// Pass 1 of column 0, 1, 3, 5 or 7 -> workspace rows 0-1.
+DHD void idct2_pass1(const int32_t* c, const int32_t* q, int32_t* w) {
+  int32_t in[8], o[2];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) in[r] = mul_w32(c[r], q[r]);
+  idct2_core(in, o);
+  w[0] = simd_descale(o[0], kConstBits - kPass1Bits + 2);
+  w[1] = simd_descale(o[1], kConstBits - kPass1Bits + 2);
+}
+// Pass 2 of one workspace row -> 2 samples.
+DHD void idct2_pass2(const int32_t* w, uint8_t* out) {
+  int32_t o[2];
+  idct2_core(w, o);
+  out[0] = range_limit8(simd_descale(o[0], kConstBits + kPass1Bits + 3 + 2));
+  out[1] = range_limit8(simd_descale(o[1], kConstBits + kPass1Bits + 3 + 2));
+}
+
+// jpeg_idct_1x1: the block's average from its DC alone.
+DHD uint8_t idct1_sample(int32_t dc, int32_t q0) { return range_limit8(simd_descale(mul_w32(dc, q0), 3)); }
+
+// Whole block at `size` 4, 2 or 1 (host model; k_idct_red runs one column / row per lane).
+DHD void idct_block_red(const int16_t* coef, const uint16_t* q, int size, uint8_t* out, int64_t pitch) {
+  if (size == 1) {
+    out[0] = idct1_sample(coef[0], (int32_t)(int16_t)q[0]);
+    return;
+  }
+  int32_t ws[4][8] = {};
+  for (int c = 0; c < 8; ++c) {
+    if (size == 4 ? c == 4 : (c != 0 && !(c & 1))) continue;
+    int32_t cc[8], qq[8], w[4];
+    for (int r = 0; r < 8; ++r) {
+      cc[r] = coef[r * 8 + c];
+      qq[r] = (int32_t)(int16_t)q[r * 8 + c];
+    }
+    if (size == 4) idct4_pass1(cc, qq, w);
+    else idct2_pass1(cc, qq, w);
+    for (int r = 0; r < size; ++r) ws[r][c] = w[r];
+  }
+  for (int r = 0; r < size; ++r) {
+    if (size == 4) idct4_pass2(ws[r], out + r * pitch);
+    else idct2_pass2(ws[r], out + r * pitch);
+  }
+}
+
 }  // namespace dino

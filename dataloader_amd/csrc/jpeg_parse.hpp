@@ -124,6 +124,7 @@ DHD int parse_jpeg(const uint8_t* p, int64_t len, int max_dim, ImgDesc* d, bool 
   d->n_scans = 0;
   d->qt_seen_mask = 0;
   d->aug_status = 0;
+  d->draft_shift = 0;  // (k_draft alone sets it)
   d->rst_bad = 0;
   d->ent_len = d->n_rst = d->terminated = 0;  // (k_destuff_write fills them for a kind-0 image)
   d->total_blocks = 0;

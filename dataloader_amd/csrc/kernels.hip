@@ -28,11 +28,13 @@
 //   kernels_small.inc               k_masks (iBOT), k_bf16_to_fp8 (Stage 5), k_copy_rgb*, k_info
 //   kernels_timer.inc               host: KernelTimer, DINO_SYNC_CHECK
 //   kernels_png.inc                 k_pnghead, k_pngwalk, k_inflate, k_unfilter (opt-in)
+//   kernels_draft.inc               k_draft, k_idct_red, k_color_red: reduced-size JPEG decode (opt-in)
 //   kernels_launch.inc              host: init_launch_geom and every launch_*; k_pixel_ops
 // A fragment is text of this file, inside namespace dino: it includes nothing, is never compiled
 // on its own, and may use whatever stands before it.
 #include "augment.hpp"
 #include "color.hpp"
+#include "draft.hpp"
 #include "huffman.hpp"
 #include "idct.hpp"
 #include "jpeg_parse.hpp"
@@ -2388,6 +2390,7 @@ __device__ __forceinline__ void idct_image(const ImgDesc* __restrict__ desc, uin
   const ImgDesc& d = desc[bk.y];
   if (d.status != DINO_IMG_OK || d.kind == 2 || (d.ncomp > kMaxComp) != (kComps > kMaxComp)) return;
   if (kComps > kMaxComp && d.kind == kPngKind) return;  // (a PNG's ncomp is 4 too: k_idct4 only)
+  if (d.draft_shift != 0) return;  // decoded at reduced size: k_idct_red
   // kind 1 (progressive / multi-scan): dense int16 coefficients in natural order,
   // component planes of bw x bh blocks (k_prog); kind 0: sparse entries + block records
   const bool dense = d.kind == 1;
@@ -2627,6 +2630,7 @@ __global__ void __launch_bounds__(256) k_color(const uint8_t* __restrict__ bytes
     return;
   }
   if (d.ncomp == 4) return;  // CMYK / YCCK: k_color4
+  if (d.draft_shift != 0) return;  // decoded at reduced size: k_color_red
   const int nc = d.ncomp;
   const PlaneView p0 = make_plane_view(d, ws, 0);
   const PlaneView p1 = nc > 1 ? make_plane_view(d, ws, 1) : p0;
@@ -3509,6 +3513,7 @@ __global__ void __launch_bounds__(kVFinalThreads) k_vfinal(const ImgDesc* __rest
 #include "kernels_small.inc"
 #include "kernels_timer.inc"
 #include "kernels_png.inc"
+#include "kernels_draft.inc"
 #include "kernels_launch.inc"
 
 }  // namespace dino

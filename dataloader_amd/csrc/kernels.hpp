@@ -33,7 +33,7 @@ struct ViewPlan {
 enum KernelId : int {
   kKParse = 0, kKPlan, kKDestuff, kKHuff1, kKIdct, kKColor, kKParams, kKVplan, kKRcoeffs, kKHresize,
   kKFinalGlobal, kKFinalLocal, kKVertGlobal, kKVertLocal, kKDcscan, kKHtab, kKHseg, kKHuff2, kKHuff3, kKProg,
-  kKPwalk, kKPlscan, kKPapply, kKPng, kKNumKernels
+  kKPwalk, kKPlscan, kKPapply, kKPng, kKDraft, kKIdctRed, kKColorRed, kKNumKernels
 };
 
 struct KernelTimer {
@@ -93,6 +93,7 @@ struct DecodeArgs {
   PCtl* pctl;
   int32_t four_component;   // 1: four-component frames decode (dino_ctx_set_four_component), 0: DINO_IMG_UNSUPPORTED
   int32_t png;              // 1: PNG files decode (dino_ctx_set_png), 0: DINO_IMG_CORRUPT as any non-JPEG
+  int32_t draft;            // N > 0: JPEGs decode at Pillow's draft("RGB", (N, N)) size (dino_ctx_set_draft), 0: full size
 };
 
 // Output pointers travel as a kernel argument (no host->device copy whose source

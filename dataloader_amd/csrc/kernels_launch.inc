@@ -11,7 +11,7 @@ static const char* const kKernelNames[kKNumKernels] = {"k_parse", "k_plan", "k_d
                                                        "k_final_global", "k_final_local", "k_vert_global",
                                                        "k_vert_local", "k_dcscan", "k_htab", "k_hseg", "k_huff2",
                                                        "k_huff3", "k_prog", "k_pwalk", "k_plscan",
-                                                       "k_papply", "k_png"};
+                                                       "k_papply", "k_png", "k_draft", "k_idct_red", "k_color_red"};
 const char* g_failed_kernel = "";
 
 #define TIMED(tm, kid, s, launch)                          \
@@ -101,6 +101,8 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
                                                   a.desc)));
   // a context with dino_ctx_set_png on: PNG files get their descriptor before the plan
   if (a.png) TIMED(tm, kKPng, s, (k_pnghead<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.max_dim, a.desc)));
+  // a context with dino_ctx_set_draft on: the JPEGs that scale get their reduced size before the plan
+  if (a.draft > 0) TIMED(tm, kKDraft, s, (k_draft<<<(B + 63) / 64, 64, 0, s>>>(a.desc, B, a.draft)));
   // (k_plan<true> also sizes kind-4 images; without the option there is none and k_plan<false> is the code it was)
   if (a.png) TIMED(tm, kKPlan, s, (k_plan<true><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
   else TIMED(tm, kKPlan, s, (k_plan<false><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
@@ -126,6 +128,10 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
   if (a.four_component) TIMED(tm, kKIdct, s, (k_idct4<<<dim3(kIdctWgs, B), 256, 0, s>>>(a.desc, a.ws)));
   TIMED(tm, kKColor, s, (k_color<<<dim3(kColorWgs, B), 256, 0, s>>>(a.bytes, a.offsets, a.desc, a.ws)));
   if (a.four_component) TIMED(tm, kKColor, s, (k_color4<<<dim3(kColorWgs, B), 256, 0, s>>>(a.desc, a.ws)));
+  if (a.draft > 0) {  // the images k_draft scaled (k_idct and k_color left them alone): no other context has one
+    TIMED(tm, kKIdctRed, s, (k_idct_red<<<dim3(kIdctWgs, B), 256, 0, s>>>(a.desc, a.ws)));
+    TIMED(tm, kKColorRed, s, (k_color_red<<<dim3(kColorWgs, B), 256, 0, s>>>(a.desc, a.ws)));
+  }
   if (a.png) {  // PNG images (kind 4): no other context has one
     TIMED(tm, kKPng, s, (k_pngwalk<<<B, kPngWalkThreads, 0, s>>>(a.bytes, a.offsets, a.lengths, a.desc, a.ws, a.pctl)));
     TIMED(tm, kKPng, s, (k_inflate<<<min(B, a.geom.grid_inf), 64, 0, s>>>(a.desc, a.ws, a.pctl, B)));

@@ -11,6 +11,11 @@ namespace dino {
 
 constexpr int32_t kMaxImageDim = 65535;
 
+// The probes have no context: for a context with dino_ctx_set_draft on they keep reporting the
+// coded width and height, and the workspace bytes and view-scratch bounds they state are upper
+// bounds there (the RGB area and every view's scratch shrink with the image; the other regions
+// keep their full-size reservation).
+
 // One image of dino_probe / dino_probe_spans / dino_gather_probe: its info row and workspace bytes.
 inline void probe_one(const uint8_t* p, int64_t len, bool raw, int32_t max_image_dim, const dino_aug_config* cfg,
                ScanRec* scans, int32_t* info_row, int64_t* ws, int64_t* aws) {

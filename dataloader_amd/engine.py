@@ -88,6 +88,7 @@ class IngestEngine:
         self.resample_filter = 0  # set_resample_filter's choice (DINO_FILTER_*; 0: bicubic)
         self.four_component = False  # set_four_component's choice (False: CMYK / YCCK files report status 1)
         self.png = False  # set_png's choice (False: PNG files report status -1, as any non-JPEG)
+        self.draft = 0  # set_draft's choice (0: every JPEG decodes at its coded size)
 
     def _s(self) -> ctypes.c_void_p:
         return _stream_handle(self.device, self.stream)
@@ -144,7 +145,7 @@ class IngestEngine:
     KERNEL_NAMES = ["k_parse", "k_plan", "k_destuff", "k_huff1", "k_idct", "k_color", "k_params", "k_vplan",
                     "k_rcoeffs", "k_hresize", "k_final_global", "k_final_local", "k_vert_global", "k_vert_local",
                     "k_dcscan", "k_htab", "k_hseg", "k_huff2", "k_huff3", "k_prog", "k_pwalk", "k_plscan",
-                    "k_papply", "k_png"]
+                    "k_papply", "k_png", "k_draft", "k_idct_red", "k_color_red"]
 
     def set_prog_decoder(self, lanes: bool) -> None:
         """Decode this context's coefficient-buffer images with the lane decoder (``True``:
@@ -174,6 +175,15 @@ class IngestEngine:
         ``DINO_IMG_CORRUPT`` (``False``, the default) from the next call on (``dino_ctx_set_png``)."""
         _lib.check(self.lib.dino_ctx_set_png(self._ctx, int(bool(on))), "dino_ctx_set_png")
         self.png = bool(on)
+
+    def set_draft(self, n: int) -> None:
+        """Decode this context's JPEGs of one or three components at the size of Pillow's
+        ``im.draft("RGB", (n, n))`` (``fallback.draft_scale``; 1/2, 1/4 or 1/8 where the sides
+        allow), or at their coded size (0, the default), from the next call on
+        (``dino_ctx_set_draft``).  The batch info, ``copy_rgb`` and the views then refer to the
+        scaled images."""
+        _lib.check(self.lib.dino_ctx_set_draft(self._ctx, int(n)), "dino_ctx_set_draft")
+        self.draft = int(n)
 
     def set_timing(self, enable: bool) -> None:
         _lib.check(self.lib.dino_set_timing(self._ctx, int(enable)), "dino_set_timing")

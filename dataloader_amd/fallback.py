@@ -96,11 +96,32 @@ def accept_four_component(info: np.ndarray) -> np.ndarray:
     return out
 
 
-def decode_with_pillow(jpeg) -> np.ndarray | None:
-    """HWC uint8 RGB exactly as the reference decodes it (cpu.py:251), or None where it raises."""
+def check_draft(n) -> int:
+    """``jpeg_draft`` as an int: 0 is off; ``ValueError`` on a negative or non-integer value."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+        raise ValueError(f"jpeg_draft must be an integer >= 0, not {n!r}")
+    return int(n)
+
+
+def draft_scale(w: int, h: int, n: int) -> tuple[int, int, int]:
+    """(s, w2, h2): the scale and the size at which a w x h JPEG decodes under ``jpeg_draft=n``,
+    Pillow's ``im.draft("RGB", (n, n))`` rule: k = min(w // n, h // n), s the largest of 8, 4, 2,
+    1 that is <= k, and the size ceil(w / s) x ceil(h / s).  The device restates it (draft.hpp)."""
+    k = min(w // n, h // n) if n > 0 else 1
+    s = 8 if k >= 8 else 4 if k >= 4 else 2 if k >= 2 else 1
+    return s, (w + s - 1) // s, (h + s - 1) // s
+
+
+def decode_with_pillow(jpeg, draft: int = 0) -> np.ndarray | None:
+    """HWC uint8 RGB exactly as the reference decodes it (cpu.py:251), or None where it raises.
+    ``draft`` > 0: after ``im.draft("RGB", (draft, draft))``, as a context with
+    ``dino_ctx_set_draft`` on decodes a JPEG (for any other format Pillow's draft is a no-op)."""
     from PIL import Image
     try:
-        return np.asarray(Image.open(io.BytesIO(bytes(jpeg))).convert("RGB"))
+        im = Image.open(io.BytesIO(bytes(jpeg)))
+        if draft > 0:
+            im.draft("RGB", (draft, draft))
+        return np.asarray(im.convert("RGB"))
     except Exception:  # noqa: BLE001 - mirrors cpu.py:252
         return None
 
@@ -175,20 +196,21 @@ def augment_need(info: np.ndarray, cfg) -> int:
     return int(aws.value)
 
 
-def pillow_container(jpeg) -> bytes:
+def pillow_container(jpeg, draft: int = 0) -> bytes:
     """One hand-over: the Pillow decode as a raw container, or b"" where Pillow raises."""
-    rgb = decode_with_pillow(jpeg)
+    rgb = decode_with_pillow(jpeg, draft)
     return raw_container(rgb) if rgb is not None else b""
 
 
 def hand_over(jpegs: list, status: np.ndarray, mask: np.ndarray | None = None,
               pool: "HostDecoder | None" = None, four_component: str = "host",
-              kind: np.ndarray | None = None, png: str = "off") -> tuple[list, int, np.ndarray]:
+              kind: np.ndarray | None = None, png: str = "off", draft: int = 0) -> tuple[list, int, np.ndarray]:
     """Replace the images the GPU decoder does not decode (``status`` ``IMG_UNSUPPORTED`` or
     ``IMG_LIMIT``, or ``mask`` when given) by Pillow-decoded raw RGB containers (zero bytes
     where Pillow raises), in ``pool``'s worker processes when given.  With ``four_component``
     ``"device"`` and the probe's ``kind`` column, the four-component files the device decodes
-    (kind 3) stay as they are.  Returns (new list, images handed over, raw mask: uint8[B], 1
+    (kind 3) stay as they are.  ``draft``: the contexts' ``jpeg_draft`` (without a ``pool``, whose own
+    applies).  Returns (new list, images handed over, raw mask: uint8[B], 1
     where the new entry is a container — the mask dino_probe / dino_decode need to accept it)."""
     _check_four_component(four_component)
     check_png(png)
@@ -206,7 +228,7 @@ def hand_over(jpegs: list, status: np.ndarray, mask: np.ndarray | None = None,
             out[i] = f.result()
     else:
         for i in idx:
-            out[i] = pillow_container(jpegs[i])
+            out[i] = pillow_container(jpegs[i], draft)
     return out, len(idx), raw_mask_of(out, idx)
 
 
@@ -265,8 +287,9 @@ class HostDecoder:
     start or breaks, the hand-over continues in this process (same bytes, slower) with a
     ``RuntimeWarning``."""
 
-    def __init__(self, workers: int):
+    def __init__(self, workers: int, draft: int = 0):
         self.workers = max(1, int(workers))
+        self.draft = check_draft(draft)  # the pipeline's jpeg_draft: every hand-over decodes under it
         self._pool = None
         self._inline = False
 
@@ -302,11 +325,11 @@ class HostDecoder:
             self.start()
         if not self._inline:
             try:
-                return self._pool.submit(pillow_container, bytes(jpeg))
+                return self._pool.submit(pillow_container, bytes(jpeg), self.draft)
             except Exception as e:  # noqa: BLE001 - the pool broke after it started
                 self._fall_back(e)
         f = Future()
-        f.set_result(pillow_container(jpeg))
+        f.set_result(pillow_container(jpeg, self.draft))
         return f
 
     def close(self) -> None:

@@ -128,8 +128,14 @@ class MI355XAugPipeline:
                  multiscan_route: str = "auto", host_workers: int | None = None,
                  multiscan_host_max: int | None = None, prefetch: int | None = None,
                  start_host_pool: bool = False, side_ahead: int = 64, resample_filter=None,
-                 four_component: str = "host", png: str = "off"):
+                 four_component: str = "host", png: str = "off", jpeg_draft: int = 0):
         self._source = source
+        # reduced-size JPEG decode (Pillow's draft("RGB", (N, N)), 0: off): every slot and side
+        # context gets dino_ctx_set_draft and every hand-over decodes under the same draft, so a
+        # batch is consistent whichever route an image took.  k_idct4 / k_color4 do not scale
+        self._draft = fallback.check_draft(jpeg_draft)
+        if self._draft and four_component == "device":
+            raise ValueError("jpeg_draft > 0 needs four_component='host': four-component frames do not scale on the device")
         # PNG files: "off" leaves them status -1 (zeros), "host" hands them to Pillow, "device"
         # decodes the common forms in the kernels (every slot and side context gets
         # dino_ctx_set_png) and hands the rest to Pillow (fallback.accept_png)
@@ -164,7 +170,7 @@ class MI355XAugPipeline:
         self._side_hot = 0             # batches the look-ahead stays engaged for (see _pull_side)
         self._source_end = False
         workers = int(host_workers) if host_workers else min(8, os.cpu_count() or 1)
-        self._host = fallback.HostDecoder(workers)
+        self._host = fallback.HostDecoder(workers, self._draft)
         if start_host_pool:
             self._host.start()
         # "auto": the host takes a batch's coefficient-buffer images while its workers finish
@@ -235,6 +241,8 @@ class MI355XAugPipeline:
                 eng.set_four_component(True)
             if self._png == "device":
                 eng.set_png(True)
+            if self._draft:
+                eng.set_draft(self._draft)
             self._slots.append(_Slot(eng))
         self._last: _Slot = self._slots[0]          # the last launched batch
         # output sets (shape key, tensors, consumer stream), batch n -> set n % (depth + 1)
@@ -562,7 +570,7 @@ class MI355XAugPipeline:
             self._side = progside.DeviceSideDecoder(self.device, max_images=pool, max_image_dim=self._max_image_dim,
                                                     stream_set=self._stream_set, lanes=lanes,
                                                     four_component=self._four_component == "device",
-                                                    png=self._png == "device")
+                                                    png=self._png == "device", draft=self._draft)
             self.stats["side_lanes"] = lanes
         if pb.jpegs is not None:
             imgs = {int(i): pb.jpegs[i] for i in idx}
@@ -727,7 +735,7 @@ class MI355XAugPipeline:
         try:
             return f.result()
         except Exception:  # noqa: BLE001 - a broken worker pool: decode here (same bytes)
-            return fallback.pillow_container(jpeg)
+            return fallback.pillow_container(jpeg, self._draft)
 
     def _screen(self, sl: _Slot, pb: _Prepared, cfg, sizes) -> tuple[torch.Tensor, torch.Tensor, int, torch.Tensor | None]:
         """Collect a prepared batch's host decodes (re-packing the batch into its staging if

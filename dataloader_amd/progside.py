@@ -128,7 +128,7 @@ class _SideEngine:
 
     def __init__(self, device: torch.device, max_images: int, max_image_dim: int, cu_count: int = 0,
                  dedicated: bool = True, index: int = 0, stream_set: int = 0, lanes: bool = False,
-                 four_component: bool = False, png: bool = False):
+                 four_component: bool = False, png: bool = False, draft: int = 0):
         self.raw = _create_stream(device.index or 0, int(cu_count)) if dedicated else None
         self.stream = self.raw if dedicated else role_stream(device, "side", index, stream_set)
         self.eng = IngestEngine(device, max_batch=max_images, max_views=1, max_crop_size=8,
@@ -138,6 +138,8 @@ class _SideEngine:
             self.eng.set_four_component(True)
         if png:  # PNG files join the pools too (the PNG kernels run the same under either progressive decoder)
             self.eng.set_png(True)
+        if draft:  # the containers then hold the scaled images, as the batches' own contexts decode them
+            self.eng.set_draft(draft)
         self.copy = role_stream(device, "side_copy", index, stream_set)  # this context's torch stream (allocations, copies)
         self.last: torch.cuda.Event | None = None   # the engine's workspace is free once this completes
         self.keep = None                             # host / device inputs of the mini-batch in flight
@@ -197,7 +199,7 @@ class DeviceSideDecoder:
 
     def __init__(self, device: torch.device, max_images: int = WAVE_POOL, min_images: int | None = None,
                  engines: int | None = None, max_image_dim: int = 0, stream_set: int = 0, lanes: bool = False,
-                 four_component: bool = False, png: bool = False):
+                 four_component: bool = False, png: bool = False, draft: int = 0):
         import os
         # measured (scripts/route_study.py, 16 progressive per 256-image batch, dedicated queues,
         # look-ahead 64, profiles/r03_side_pools.jsonl): pools of 16 images on 2 contexts 11.2k img/s,
@@ -220,6 +222,7 @@ class DeviceSideDecoder:
         self.lanes = bool(lanes)           # the side contexts' decoder (side_plan)
         self.four_component = bool(four_component)  # the side contexts decode CMYK / YCCK files
         self.png = bool(png)                        # and the PNG files the device takes
+        self.draft = int(draft)                     # the pipeline's jpeg_draft (the probe's sizes are then upper bounds)
         self.lane_min = int(os.environ.get("DINO_SIDE_LANE_MIN", LANE_MIN_POOL))  # smaller pools: wave decoder
         self._engines: list[_SideEngine] = []
         self._rr = 0
@@ -266,7 +269,7 @@ class DeviceSideDecoder:
         if len(self._engines) < self.cap:
             e = _SideEngine(self.device, self.max_images, self.max_image_dim, self.cu_count, self.dedicated,
                             index=len(self._engines), stream_set=self.stream_set, lanes=self.lanes,
-                            four_component=self.four_component, png=self.png)
+                            four_component=self.four_component, png=self.png, draft=self.draft)
             self._engines.append(e)
             return e
         e = self._engines[self._rr % len(self._engines)]

@@ -34,8 +34,10 @@ class MI355XUserAugPipeline:
 
     def __init__(self, source: Any, spec, batch_size: int, out_dtype="bf16", device: int = 0,
                  max_image_dim: int = 0, workspace_bytes: int = 0, norm=None, resample_filter=None,
-                 png: str = "off"):
+                 png: str = "off", jpeg_draft: int = 0):
         self._source = source
+        # reduced-size JPEG decode (Pillow's draft("RGB", (N, N))): on the context and in the hand-overs
+        self._draft = fallback.check_draft(jpeg_draft)
         # PNG files: "off" leaves them zero-filled; "host" and "device" both hand every PNG Pillow may
         # decode over to it (this pipeline's context does not decode them), as four-component files are
         fallback.check_png(png)
@@ -49,6 +51,8 @@ class MI355XUserAugPipeline:
                                     max_image_dim=max_image_dim, workspace_bytes=workspace_bytes)
         if resample_filter is not None:  # Pillow filter of the resize (None: bicubic)
             self._engine.set_resample_filter(resample_filter)
+        if self._draft:
+            self._engine.set_draft(self._draft)
         self.stats = {"batches": 0, "images": 0, "status": Counter(), "host_decoded": 0}
         self._pending_status: deque = deque()
         self._closed = False
@@ -87,13 +91,18 @@ class MI355XUserAugPipeline:
         png = "off" if self._png == "off" else "host"
         if np.isin(info[:, 0], (fallback.IMG_UNSUPPORTED, fallback.IMG_LIMIT)).any() or \
                 (png != "off" and fallback.png_mask(info).any()):
-            jpegs, n, rm = fallback.hand_over(list(jpegs), info[:, 0], kind=info[:, 3], png=png)
+            jpegs, n, rm = fallback.hand_over(list(jpegs), info[:, 0], kind=info[:, 3], png=png, draft=self._draft)
             self.stats["host_decoded"] += n
             host_buf, offsets = pack_jpegs(jpegs, pin=True)
             info, ws, _ = fallback.probe(host_buf.data_ptr(), offsets.numpy(), len(jpegs), self._max_image_dim,
                                          raw_mask=rm)
             raw = torch.from_numpy(rm).pin_memory()
         ds = int(self._spec.decode_size)
+        if self._draft:  # the probe reports coded sizes: the JPEGs the context decodes come out scaled
+            info = info.copy()
+            for r in info:
+                if r[0] == 0 and r[3] in (0, 1):
+                    r[1:3] = fallback.draft_scale(int(r[1]), int(r[2]), self._draft)[1:]
         shapes = {resize_shorter_size(int(w), int(h), ds) if st == 0 else (ds, ds)
                   for st, w, h, _ in info.tolist()}
         if len(shapes) != 1:  # the reference's torch.stack raises on unequal shapes

@@ -51,7 +51,9 @@
  *    YCCK JPEGs decoded on the device, off by default) and kind 3 in the probes' info;
  *    dino_ctx_set_png (PNG files decoded on the device, off by default), kinds 4 and 5 in the
  *    probes' info, dino_kernel_times id 23, dino_debug_region 10 and 11; dino_host_alloc /
- *    dino_host_free (page-locked memory for hosts where a mapping cannot be registered).
+ *    dino_host_free (page-locked memory for hosts where a mapping cannot be registered);
+ *    dino_ctx_set_draft (JPEGs decoded at Pillow's Image.draft size, off by default) and
+ *    dino_kernel_times ids 24 to 26.
  */
 #ifndef DINO_INGEST_H
 #define DINO_INGEST_H
@@ -377,6 +379,21 @@ int dino_ctx_set_four_component(dino_ctx* ctx, int32_t on);
  * the Adler-32) is not examined.  dino_kernel_times id 23 ("k_png") sums the four PNG
  * kernels; dino_debug_region 10 is the joined zlib stream, 11 the inflated, still-filtered rows. */
 int dino_ctx_set_png(dino_ctx* ctx, int32_t on);
+
+/* Reduced-size JPEG decode on this ctx, from the next call on: n = 0 (default) decodes every
+ * image at its coded size; n > 0 decodes each JPEG of one or three components as
+ *   im = Image.open(..); im.draft("RGB", (n, n)); im.convert("RGB")
+ * does, bit for bit on encoder-valid data: with k = min(W / n, H / n) (integer division) the
+ * scale s is the largest of 8, 4, 2, 1 that is <= k, the image is ceil(W / s) x ceil(H / s), and
+ * libjpeg's 4x4 / 2x2 / 1x1 inverse DCTs make it (baseline and progressive, either progressive
+ * decoder).  dino_batch_info, dino_copy_rgb*, the view records and the views then refer to the
+ * scaled image.  Raw containers, PNGs and four-component frames do not scale (a caller that
+ * hands images over applies the same draft on the host).  The probes have no ctx and keep
+ * reporting the coded size: their workspace and view-scratch numbers are upper bounds for such a
+ * ctx.  n < 0: DINO_EINVAL.  dino_kernel_times ids 24 ("k_draft"), 25 ("k_idct_red") and 26
+ * ("k_color_red") time its kernels.  What a damaged stream's out-of-range coefficients give at
+ * reduced size is not pinned against Pillow. */
+int dino_ctx_set_draft(dino_ctx* ctx, int32_t n);
 
 /* The coefficient code of the resample kernels run on the host (no GPU involved; tests and
  * introspection): for in_size -> out_size with `filter`, *ksize = taps reserved per output;
