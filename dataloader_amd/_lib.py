@@ -99,6 +99,10 @@ def load() -> ctypes.CDLL:
         "dino_ctx_set_four_component": (i32, [vp, i32]),
         "dino_ctx_set_png": (i32, [vp, i32]),
         "dino_ctx_set_draft": (i32, [vp, i32]),
+        "dino_ctx_set_exif_transpose": (i32, [vp, i32]),
+        "dino_probe_orient": (i32, [vp, vp, i32, vp]),
+        "dino_orient_map": (i32, [i32, i32, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+        "dino_orient_tile": (i32, []),
         "dino_resample_coeffs_host": (i32, [i32, i32, i32, i32, i32, vp, vp, vp]),
         "dino_kernel_times": (i32, [vp, vp, vp, i32]),
         "dino_tar_index": (i32, [vp, i64, vp, i64, vp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
@@ -143,4 +147,5 @@ def exported_symbols() -> list[str]:
             "dino_feed_next", "dino_feed_copy", "dino_feed_release", "dino_feed_reset", "dino_feed_stats",
             "dino_feed_last_error", "dino_stream_create", "dino_stream_destroy",
             "dino_ctx_set_resample_filter", "dino_resample_coeffs_host", "dino_ctx_set_four_component", "dino_ctx_set_png",
-            "dino_ctx_set_draft"]
+            "dino_ctx_set_draft", "dino_ctx_set_exif_transpose", "dino_probe_orient", "dino_orient_map",
+            "dino_orient_tile"]

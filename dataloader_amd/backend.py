@@ -122,7 +122,8 @@ class MI355XBackend:
     def __init__(self, max_image_dim: int = 0, workspace_bytes: int = 0, max_in_flight: int = 3,
                  hbm_fraction: float = 0.15, host_workers: int | None = None, multiscan_route: str = "side",
                  side_ahead: int | None = None, resample_filter: str | None = None,
-                 four_component: str = "host", png: str = "off", jpeg_draft: int = 0) -> None:
+                 four_component: str = "host", png: str = "off", jpeg_draft: int = 0,
+                 exif_transpose: bool = False) -> None:
         # Pillow filter of every resize: None = bicubic everywhere (CPUBackend parity, which
         # ignores EvalAugSpec.interpolation too); a filter's name applies to every recipe;
         # "spec" honours EvalAugSpec.interpolation as the reference's GPU peer does
@@ -155,6 +156,11 @@ class MI355XBackend:
         self._jpeg_draft = check_draft(jpeg_draft)
         if self._jpeg_draft and four_component == "device":
             raise ValueError("jpeg_draft > 0 needs four_component='host': four-component frames do not scale on the device")
+        # EXIF orientation, off by default (CPUBackend ignores the tag): True gives every image as
+        # ImageOps.exif_transpose(im).convert("RGB") does, which is what the reference's DALI
+        # backend's decoder does by default.  The device turns the JPEGs whose tag its walk
+        # verifies (k_orient); Pillow decides the rest through the hand-over
+        self._exif_transpose = bool(exif_transpose)
         self._max_image_dim = max_image_dim
         self._workspace_bytes = workspace_bytes
         self._max_in_flight = max(1, int(max_in_flight))
@@ -265,7 +271,7 @@ class MI355XBackend:
                                          out_dtype=pipeline_cfg.output_dtype, device=pipeline_cfg.device_id,
                                          max_image_dim=self._max_image_dim, workspace_bytes=self._workspace_bytes,
                                          norm=norm, resample_filter=self.spec_filter(aug_spec), png=self._png,
-                                         jpeg_draft=self._jpeg_draft)
+                                         jpeg_draft=self._jpeg_draft, exif_transpose=self._exif_transpose)
         if _is_dinov2_spec(aug_spec):
             aug_cfg = aug_spec.aug_cfg
             names = None
@@ -311,6 +317,7 @@ class MI355XBackend:
             four_component=self._four_component,
             png=self._png,
             jpeg_draft=self._jpeg_draft,
+            exif_transpose=self._exif_transpose,
         )
 
     def build_pipeline_iterator(self, pipeline: Any, aug_spec: Any, output_map: list[str],

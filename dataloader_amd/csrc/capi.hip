@@ -17,6 +17,7 @@
 
 #include <hip/hip_ext.h>
 
+#include "exif_parse.hpp"
 #include "hostcopy.hpp"
 #include "jpeg_parse.hpp"
 #include "kernels.hpp"
@@ -66,6 +67,8 @@ struct dino_ctx {
   int32_t four_component = 0; // dino_ctx_set_four_component: read at each decode launch
   int32_t png = 0;            // dino_ctx_set_png: read at each decode launch
   int32_t draft = 0;          // dino_ctx_set_draft: read at each decode launch
+  int32_t exif_transpose = 0; // dino_ctx_set_exif_transpose: read at each decode launch
+  OCtl* d_octl = nullptr;     // k_orient's tiles (allocated by the first dino_ctx_set_exif_transpose(ctx, 1))
   KernelTimer* timer = nullptr;
   KernelTimer* tm() { return timer && timer->enabled ? timer : nullptr; }
 };
@@ -135,6 +138,7 @@ int dino_ctx_destroy(dino_ctx* c) {
   (void)hipFree(c->d_params);
   (void)hipFree(c->d_gcrop);
   (void)hipFree(c->d_pctl);
+  (void)hipFree(c->d_octl);
   if (c->timer) {
     c->timer->destroy();
     delete c->timer;
@@ -150,7 +154,8 @@ int dino_decode_spans(dino_ctx* c, const uint8_t* d_bytes, const int64_t* d_offs
     return fail(DINO_EINVAL, "dino_decode: batch %s%lld exceeds ctx max_batch", "", batch);
   hipStream_t s = (hipStream_t)stream;
   DecodeArgs a{d_bytes, d_offsets, d_lengths, d_raw_mask, batch, c->lim.max_image_dim, c->d_desc, c->d_ws,
-               c->ws_size, c->geom, c->d_pctl, c->four_component, c->png, c->draft};
+               c->ws_size, c->geom, c->d_pctl, c->four_component, c->png, c->draft,
+               c->exif_transpose ? c->d_octl : nullptr};
   hipError_t e = launch_decode(a, s, c->tm());
   if (e != hipSuccess) return hip_fail(e, "dino_decode");
   if (d_info && (e = launch_info(c->d_desc, batch, d_info, s)) != hipSuccess) return hip_fail(e, "dino_decode(info)");
@@ -592,6 +597,33 @@ int dino_ctx_set_draft(dino_ctx* c, int32_t n) {
   c->draft = n;  // read at each launch (launch_decode)
   return DINO_OK;
 }
+
+int dino_ctx_set_exif_transpose(dino_ctx* c, int32_t on) {
+  if (!c) return fail(DINO_EINVAL, "dino_ctx_set_exif_transpose: null ctx%s%lld");
+  if (on && !c->d_octl) {
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->d_octl, octl_bytes(c->lim.max_batch));
+    if (e != hipSuccess) return hip_fail(e, "dino_ctx_set_exif_transpose: hipMalloc");
+  }
+  c->exif_transpose = on != 0;  // read at each launch (launch_decode)
+  return DINO_OK;
+}
+
+int dino_probe_orient(const uint64_t* ptrs, const int64_t* lens, int32_t batch, uint8_t* out) {
+  if (batch < 0 || (batch > 0 && (!ptrs || !lens || !out))) return fail(DINO_EINVAL, "dino_probe_orient: bad arguments%s%lld");
+  for (int32_t i = 0; i < batch; ++i)
+    out[i] = lens[i] > 0 ? (uint8_t)exif_orientation((const uint8_t*)(uintptr_t)ptrs[i], lens[i]) : (uint8_t)kOrientNone;
+  return DINO_OK;
+}
+
+int dino_orient_map(int32_t orientation, int32_t w, int32_t h, int32_t x, int32_t y, int32_t* ox, int32_t* oy) {
+  if (orientation < 1 || orientation > 8 || !ox || !oy || x < 0 || y < 0 || x >= w || y >= h)
+    return fail(DINO_EINVAL, "dino_orient_map: bad arguments%s%lld");
+  orient_forward(orientation, w, h, x, y, ox, oy);
+  return DINO_OK;
+}
+
+int dino_orient_tile(void) { return kOrientTile; }
 
 int dino_ctx_set_resample_filter(dino_ctx* c, int32_t filter) {
   if (!c) return fail(DINO_EINVAL, "dino_ctx_set_resample_filter: null ctx%s%lld");

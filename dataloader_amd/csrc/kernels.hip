@@ -29,12 +29,14 @@
 //   kernels_timer.inc               host: KernelTimer, DINO_SYNC_CHECK
 //   kernels_png.inc                 k_pnghead, k_pngwalk, k_inflate, k_unfilter (opt-in)
 //   kernels_draft.inc               k_draft, k_idct_red, k_color_red: reduced-size JPEG decode (opt-in)
+//   kernels_orient.inc              k_exif, k_orient_scan, k_orient, k_orient_done: EXIF orientation applied (opt-in)
 //   kernels_launch.inc              host: init_launch_geom and every launch_*; k_pixel_ops
 // A fragment is text of this file, inside namespace dino: it includes nothing, is never compiled
 // on its own, and may use whatever stands before it.
 #include "augment.hpp"
 #include "color.hpp"
 #include "draft.hpp"
+#include "exif_parse.hpp"
 #include "huffman.hpp"
 #include "idct.hpp"
 #include "jpeg_parse.hpp"
@@ -269,7 +271,7 @@ struct ImgItem {
   __device__ operator ImgSum() const { return {z.total(), ds}; }
 };
 
-template <bool kPng>
+template <bool kPng, bool kOrient = false>
 __global__ void __launch_bounds__(1024) k_plan(ImgDesc* __restrict__ desc, int B, int64_t ws_size,
                                               PCtl* __restrict__ pctl) {
   if (threadIdx.x == 0) {  // the batch's coefficient-buffer registry (k_pwalk, k_pscan, k_plscan)
@@ -282,7 +284,7 @@ __global__ void __launch_bounds__(1024) k_plan(ImgDesc* __restrict__ desc, int B
     pctl->lmax_scans = 0;
   }
   scan_and_place<ImgSum>(
-      B, ws_size, [&](int i) { return ImgItem{image_chunk_bytes<kPng>(desc[i]), ds_parts(desc[i])}; },
+      B, ws_size, [&](int i) { return ImgItem{image_chunk_bytes<kPng, kOrient>(desc[i]), ds_parts(desc[i])}; },
       [&](int i, const ImgItem& v, const ImgSum& base, bool placed) {
         ImgDesc& d = desc[i];
         d.ds_item_base = base.ds;
@@ -3514,6 +3516,7 @@ __global__ void __launch_bounds__(kVFinalThreads) k_vfinal(const ImgDesc* __rest
 #include "kernels_timer.inc"
 #include "kernels_png.inc"
 #include "kernels_draft.inc"
+#include "kernels_orient.inc"
 #include "kernels_launch.inc"
 
 }  // namespace dino

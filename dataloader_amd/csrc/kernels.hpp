@@ -33,7 +33,7 @@ struct ViewPlan {
 enum KernelId : int {
   kKParse = 0, kKPlan, kKDestuff, kKHuff1, kKIdct, kKColor, kKParams, kKVplan, kKRcoeffs, kKHresize,
   kKFinalGlobal, kKFinalLocal, kKVertGlobal, kKVertLocal, kKDcscan, kKHtab, kKHseg, kKHuff2, kKHuff3, kKProg,
-  kKPwalk, kKPlscan, kKPapply, kKPng, kKDraft, kKIdctRed, kKColorRed, kKNumKernels
+  kKPwalk, kKPlscan, kKPapply, kKPng, kKDraft, kKIdctRed, kKColorRed, kKExif, kKOrient, kKNumKernels
 };
 
 struct KernelTimer {
@@ -64,6 +64,7 @@ struct LaunchGeom {
   int32_t grid_hr;   // persistent k_hresize grid (occupancy x CUs)
   int32_t vfinal_max_s;  // views up to this size take the fused k_vfinal (DINO_VFINAL_MAX_S, at most 128)
   int32_t grid_inf;  // persistent k_inflate grid (one-wave workgroups; contexts with dino_ctx_set_png on)
+  int32_t grid_or;   // persistent k_orient grid (contexts with dino_ctx_set_exif_transpose on)
 };
 
 // Coefficient-buffer images of a batch (k_plan zeroes, k_pwalk registers, k_pscan
@@ -78,6 +79,16 @@ struct PCtl {
 };
 DHD int64_t pctl_bytes(int max_batch) { return 32 + 4 * (int64_t)(max_batch > 0 ? max_batch : 1); }
 hipError_t init_launch_geom(int device, LaunchGeom* g);
+
+// The tiles k_orient turns (a context with dino_ctx_set_exif_transpose on; k_orient_scan fills it):
+// image i owns the tickets [base[i], base[i + 1]), its kOrientTile x kOrientTile tiles in row
+// order, none for an image that stays as it is; base[batch] = total.
+constexpr int kOrientTile = 64;
+struct OCtl {
+  uint32_t ticket, total;
+  int32_t base[1];  // [max_batch + 1]
+};
+DHD int64_t octl_bytes(int max_batch) { return 8 + 4 * ((int64_t)(max_batch > 0 ? max_batch : 1) + 1); }
 
 struct DecodeArgs {
   const uint8_t* bytes;
@@ -94,6 +105,7 @@ struct DecodeArgs {
   int32_t four_component;   // 1: four-component frames decode (dino_ctx_set_four_component), 0: DINO_IMG_UNSUPPORTED
   int32_t png;              // 1: PNG files decode (dino_ctx_set_png), 0: DINO_IMG_CORRUPT as any non-JPEG
   int32_t draft;            // N > 0: JPEGs decode at Pillow's draft("RGB", (N, N)) size (dino_ctx_set_draft), 0: full size
+  OCtl* octl;               // non-null: JPEGs leave the decode upright (dino_ctx_set_exif_transpose), null: as coded
 };
 
 // Output pointers travel as a kernel argument (no host->device copy whose source

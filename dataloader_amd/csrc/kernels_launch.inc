@@ -11,7 +11,8 @@ static const char* const kKernelNames[kKNumKernels] = {"k_parse", "k_plan", "k_d
                                                        "k_final_global", "k_final_local", "k_vert_global",
                                                        "k_vert_local", "k_dcscan", "k_htab", "k_hseg", "k_huff2",
                                                        "k_huff3", "k_prog", "k_pwalk", "k_plscan",
-                                                       "k_papply", "k_png", "k_draft", "k_idct_red", "k_color_red"};
+                                                       "k_papply", "k_png", "k_draft", "k_idct_red", "k_color_red",
+                                                       "k_exif", "k_orient"};
 const char* g_failed_kernel = "";
 
 #define TIMED(tm, kid, s, launch)                          \
@@ -87,6 +88,7 @@ hipError_t init_launch_geom(int device, LaunchGeom* g) {
   // inflate waves (PNG): four per CU fit its LDS (kInfLdsBytes each); DINO_INFLATE_WAVES sets the grid
   const char* iw = getenv("DINO_INFLATE_WAVES");
   g->grid_inf = iw && atoi(iw) > 0 ? atoi(iw) : 4 * cus;
+  g->grid_or = 4 * cus;  // k_orient: 16.3 KiB of LDS and four waves a workgroup
   // the lane decoder is opt-in (DINO_PROG_LANE=1): its throughput is higher but a scan's latency
   // is ~3x a scan wave's, more than the side route's look-ahead covers (DESIGN.md §5)
   const char* pl = getenv("DINO_PROG_LANE");
@@ -103,8 +105,16 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
   if (a.png) TIMED(tm, kKPng, s, (k_pnghead<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.max_dim, a.desc)));
   // a context with dino_ctx_set_draft on: the JPEGs that scale get their reduced size before the plan
   if (a.draft > 0) TIMED(tm, kKDraft, s, (k_draft<<<(B + 63) / 64, 64, 0, s>>>(a.desc, B, a.draft)));
-  // (k_plan<true> also sizes kind-4 images; without the option there is none and k_plan<false> is the code it was)
-  if (a.png) TIMED(tm, kKPlan, s, (k_plan<true><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
+  // a context with dino_ctx_set_exif_transpose on: every image gets its orientation before the plan
+  if (a.octl) {
+    TIMED(tm, kKExif, s, (k_exif<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.desc)));
+    TIMED(tm, kKExif, s, (k_orient_scan<<<1, 1024, 0, s>>>(a.desc, B, a.octl)));
+  }
+  // (k_plan<true> also sizes kind-4 images; without the option there is none and k_plan<false> is the code it was;
+  // k_plan<.., true> gives the images that turn their second RGB region)
+  if (a.octl && a.png) TIMED(tm, kKPlan, s, (k_plan<true, true><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
+  else if (a.octl) TIMED(tm, kKPlan, s, (k_plan<false, true><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
+  else if (a.png) TIMED(tm, kKPlan, s, (k_plan<true><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
   else TIMED(tm, kKPlan, s, (k_plan<false><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
   const int grid_ds = a.geom.grid_ds, grid1 = a.geom.grid1, grid3 = a.geom.grid3;
   TIMED(tm, kKDestuff, s, (k_destuff_count<<<grid_ds, kDestuffThreads, 0, s>>>(a.bytes, a.offsets, B, a.desc, a.ws)));
@@ -136,6 +146,10 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
     TIMED(tm, kKPng, s, (k_pngwalk<<<B, kPngWalkThreads, 0, s>>>(a.bytes, a.offsets, a.lengths, a.desc, a.ws, a.pctl)));
     TIMED(tm, kKPng, s, (k_inflate<<<min(B, a.geom.grid_inf), 64, 0, s>>>(a.desc, a.ws, a.pctl, B)));
     TIMED(tm, kKPng, s, (k_unfilter<<<B, 64, 0, s>>>(a.desc, a.ws)));
+  }
+  if (a.octl) {  // after every colour stage: the images k_exif tagged turn, then show their upright side
+    TIMED(tm, kKOrient, s, (k_orient<<<a.geom.grid_or, 256, 0, s>>>(a.desc, a.ws, a.octl, B)));
+    TIMED(tm, kKExif, s, (k_orient_done<<<(B + 63) / 64, 64, 0, s>>>(a.desc, B)));
   }
   return hipGetLastError();
 }

@@ -82,14 +82,24 @@ DHD DsRole ds_part_role(int part, int lead, int n, int E, int ds_items) {
   return {k0 < E, E < n ? (E >= k0 && E < k1) : part == ds_items - 1};
 }
 
+// The RGB region of a w x h image, and what an image that k_orient turns (orientation 2..8 in
+// ImgDesc::pad0[0], k_exif) adds to its chunk: a second region of that size right after the
+// first, into which k_orient writes the upright image (a non-square transpose has no in-place
+// form).  orient_extra_bytes bounds what that adds to the chunk's total after its 256-byte round.
+DHD int64_t rgb_region_bytes(int64_t w, int64_t h) { return align16(w * h * 3 + 16); }
+DHD int64_t orient_extra_bytes(int64_t w, int64_t h) { return align256(rgb_region_bytes(w, h)); }
+
 // kPng: the caller may hold PNG images (kind 4).  k_plan of a context without dino_ctx_set_png is
-// instantiated without them and stays the code it was.
-template <bool kPng = true>
+// instantiated without them and stays the code it was.  kOrient: the caller's k_exif wrote every
+// image's orientation (dino_ctx_set_exif_transpose); without it pad0 is not read and the layout
+// is the one it was.
+template <bool kPng = true, bool kOrient = false>
 DHD ChunkSizes image_chunk_bytes(const ImgDesc& d) {
   ChunkSizes z{};
   if (d.status != DINO_IMG_OK) return z;
-  z.rgb = align16((int64_t)d.width * d.height * 3 + 16);
+  z.rgb = rgb_region_bytes(d.width, d.height);
   if (d.kind == 2) return chunk_finish(z);
+  if (kOrient && d.pad0[0] >= 2) z.rgb *= 2;
   if (kPng && d.kind == kPngKind) {  // the joined zlib stream, one carried row, the filtered rows, the palette
     z.ent = align16((int64_t)d.scan_len + 64);
     z.coef = align16((int64_t)d.width * 4 + 16);

@@ -89,6 +89,7 @@ class IngestEngine:
         self.four_component = False  # set_four_component's choice (False: CMYK / YCCK files report status 1)
         self.png = False  # set_png's choice (False: PNG files report status -1, as any non-JPEG)
         self.draft = 0  # set_draft's choice (0: every JPEG decodes at its coded size)
+        self.exif_transpose = False  # set_exif_transpose's choice (False: the Orientation tag is ignored)
 
     def _s(self) -> ctypes.c_void_p:
         return _stream_handle(self.device, self.stream)
@@ -145,7 +146,7 @@ class IngestEngine:
     KERNEL_NAMES = ["k_parse", "k_plan", "k_destuff", "k_huff1", "k_idct", "k_color", "k_params", "k_vplan",
                     "k_rcoeffs", "k_hresize", "k_final_global", "k_final_local", "k_vert_global", "k_vert_local",
                     "k_dcscan", "k_htab", "k_hseg", "k_huff2", "k_huff3", "k_prog", "k_pwalk", "k_plscan",
-                    "k_papply", "k_png", "k_draft", "k_idct_red", "k_color_red"]
+                    "k_papply", "k_png", "k_draft", "k_idct_red", "k_color_red", "k_exif", "k_orient"]
 
     def set_prog_decoder(self, lanes: bool) -> None:
         """Decode this context's coefficient-buffer images with the lane decoder (``True``:
@@ -184,6 +185,16 @@ class IngestEngine:
         scaled images."""
         _lib.check(self.lib.dino_ctx_set_draft(self._ctx, int(n)), "dino_ctx_set_draft")
         self.draft = int(n)
+
+    def set_exif_transpose(self, on: bool) -> None:
+        """Decode this context's JPEGs as ``ImageOps.exif_transpose(im).convert("RGB")`` gives them
+        (``True``) or with the Orientation tag ignored (``False``, the default), from the next
+        call on (``dino_ctx_set_exif_transpose``).  The batch info, ``copy_rgb`` and the views
+        then refer to the upright images.  The files whose tag the device does not verify
+        (``fallback.probe_orient``: 255) decode unturned: handing them to Pillow is the caller's
+        job, as is adding ``fallback.orient_need`` to the decode workspace before ``reserve``."""
+        _lib.check(self.lib.dino_ctx_set_exif_transpose(self._ctx, int(bool(on))), "dino_ctx_set_exif_transpose")
+        self.exif_transpose = bool(on)
 
     def set_timing(self, enable: bool) -> None:
         _lib.check(self.lib.dino_set_timing(self._ctx, int(enable)), "dino_set_timing")

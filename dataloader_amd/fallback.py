@@ -112,15 +112,75 @@ def draft_scale(w: int, h: int, n: int) -> tuple[int, int, int]:
     return s, (w + s - 1) // s, (h + s - 1) // s
 
 
-def decode_with_pillow(jpeg, draft: int = 0) -> np.ndarray | None:
+ORIENT_UNVERIFIED = 255  # dino_probe_orient: Pillow decides (the image is handed over)
+
+
+def probe_orient(ptrs: np.ndarray, lens: np.ndarray) -> np.ndarray:
+    """``dino_probe_orient`` over images where they lie (absolute host addresses + lengths):
+    uint8[B], 0 where a context with ``dino_ctx_set_exif_transpose`` on leaves the image as it
+    is, 2..8 where it turns it, ``ORIENT_UNVERIFIED`` where its walk verifies neither."""
+    p = np.ascontiguousarray(ptrs, np.uint64)
+    n = np.ascontiguousarray(lens, np.int64)
+    out = np.zeros(len(p), np.uint8)
+    _lib.check(_lib.load().dino_probe_orient(p.ctypes.data_as(ctypes.c_void_p), n.ctypes.data_as(ctypes.c_void_p),
+                                             len(p), out.ctypes.data_as(ctypes.c_void_p)), "dino_probe_orient")
+    return out
+
+
+def probe_orient_list(images: list) -> np.ndarray:
+    """``probe_orient`` over a list of ``bytes``."""
+    from .tario import spans_of
+    ptrs, lens, _keep = spans_of(images)
+    return probe_orient(ptrs, lens)
+
+
+def orient_map(orientation: int, w: int, h: int, x: int, y: int) -> tuple[int, int]:
+    """Where EXIF orientation 1..8 sends pixel (x, y) of a w x h image: the mapping ``k_orient``
+    applies (``dino_orient_map``, exif_parse.hpp ``orient_forward``)."""
+    ox, oy = ctypes.c_int32(0), ctypes.c_int32(0)
+    _lib.check(_lib.load().dino_orient_map(orientation, w, h, x, y, ctypes.byref(ox), ctypes.byref(oy)), "dino_orient_map")
+    return ox.value, oy.value
+
+
+def accept_orient(info: np.ndarray, orient: np.ndarray, cfg=None) -> tuple[np.ndarray, int, int]:
+    """The probe's info as contexts with ``dino_ctx_set_exif_transpose`` on decode the batch,
+    and the decode- and augment-workspace bytes to add to the probe's.  Among the rows the device decodes
+    (status 0, not a container: ``orient`` is 0 there), those with ``ORIENT_UNVERIFIED`` become
+    ``IMG_UNSUPPORTED`` (handed to Pillow, which applies ``exif_transpose``), those with
+    orientation 5..8 get width and height swapped, and every one with 2..8 adds the second RGB
+    region ``k_orient`` writes (plan.hpp ``orient_extra_bytes``).  The view scratch is not
+    symmetric in width and height (the horizontal pass keeps crop_h <= H rows of S pixels), so
+    with ``cfg`` (the probe's ``dino_aug_config``) each image whose sides swap gives back
+    ``view_scratch_bound`` of its coded size and takes that of its upright size: the probe's
+    bound plus the third value is again the sum over the images as the views see them (it can be
+    negative).  A copy."""
+    out = np.array(info, np.int32, copy=True)
+    o = np.where(out[:, 0] == 0, np.asarray(orient, np.int64), 0)
+    out[o == ORIENT_UNVERIFIED, 0] = IMG_UNSUPPORTED
+    turn = (o >= 2) & (o <= 8)
+    w, h = out[:, 1].astype(np.int64), out[:, 2].astype(np.int64)
+    extra = int(((((w * h * 3 + 16 + 15) & ~15) + 255) & ~255)[turn].sum())
+    swap = turn & (o >= 5)
+    out[swap, 1], out[swap, 2] = h[swap], w[swap]
+    aws = 0
+    if cfg is not None and swap.any():
+        aws = augment_need(out[swap], cfg) - augment_need(np.asarray(info, np.int32)[swap], cfg)
+    return out, extra, aws
+
+
+def decode_with_pillow(jpeg, draft: int = 0, exif_transpose: bool = False) -> np.ndarray | None:
     """HWC uint8 RGB exactly as the reference decodes it (cpu.py:251), or None where it raises.
     ``draft`` > 0: after ``im.draft("RGB", (draft, draft))``, as a context with
-    ``dino_ctx_set_draft`` on decodes a JPEG (for any other format Pillow's draft is a no-op)."""
-    from PIL import Image
+    ``dino_ctx_set_draft`` on decodes a JPEG (for any other format Pillow's draft is a no-op).
+    ``exif_transpose``: after ``ImageOps.exif_transpose`` (and the draft), as a context with
+    ``dino_ctx_set_exif_transpose`` on decodes a JPEG whose tag it verifies."""
+    from PIL import Image, ImageOps
     try:
         im = Image.open(io.BytesIO(bytes(jpeg)))
         if draft > 0:
             im.draft("RGB", (draft, draft))
+        if exif_transpose:
+            im = ImageOps.exif_transpose(im)
         return np.asarray(im.convert("RGB"))
     except Exception:  # noqa: BLE001 - mirrors cpu.py:252
         return None
@@ -196,21 +256,22 @@ def augment_need(info: np.ndarray, cfg) -> int:
     return int(aws.value)
 
 
-def pillow_container(jpeg, draft: int = 0) -> bytes:
+def pillow_container(jpeg, draft: int = 0, exif_transpose: bool = False) -> bytes:
     """One hand-over: the Pillow decode as a raw container, or b"" where Pillow raises."""
-    rgb = decode_with_pillow(jpeg, draft)
+    rgb = decode_with_pillow(jpeg, draft, exif_transpose)
     return raw_container(rgb) if rgb is not None else b""
 
 
 def hand_over(jpegs: list, status: np.ndarray, mask: np.ndarray | None = None,
               pool: "HostDecoder | None" = None, four_component: str = "host",
-              kind: np.ndarray | None = None, png: str = "off", draft: int = 0) -> tuple[list, int, np.ndarray]:
+              kind: np.ndarray | None = None, png: str = "off", draft: int = 0,
+              exif_transpose: bool = False) -> tuple[list, int, np.ndarray]:
     """Replace the images the GPU decoder does not decode (``status`` ``IMG_UNSUPPORTED`` or
     ``IMG_LIMIT``, or ``mask`` when given) by Pillow-decoded raw RGB containers (zero bytes
     where Pillow raises), in ``pool``'s worker processes when given.  With ``four_component``
     ``"device"`` and the probe's ``kind`` column, the four-component files the device decodes
-    (kind 3) stay as they are.  ``draft``: the contexts' ``jpeg_draft`` (without a ``pool``, whose own
-    applies).  Returns (new list, images handed over, raw mask: uint8[B], 1
+    (kind 3) stay as they are.  ``draft``, ``exif_transpose``: the contexts' ``jpeg_draft`` and
+    ``exif_transpose`` (without a ``pool``, whose own apply).  Returns (new list, images handed over, raw mask: uint8[B], 1
     where the new entry is a container — the mask dino_probe / dino_decode need to accept it)."""
     _check_four_component(four_component)
     check_png(png)
@@ -228,7 +289,7 @@ def hand_over(jpegs: list, status: np.ndarray, mask: np.ndarray | None = None,
             out[i] = f.result()
     else:
         for i in idx:
-            out[i] = pillow_container(jpegs[i], draft)
+            out[i] = pillow_container(jpegs[i], draft, exif_transpose)
     return out, len(idx), raw_mask_of(out, idx)
 
 
@@ -287,9 +348,10 @@ class HostDecoder:
     start or breaks, the hand-over continues in this process (same bytes, slower) with a
     ``RuntimeWarning``."""
 
-    def __init__(self, workers: int, draft: int = 0):
+    def __init__(self, workers: int, draft: int = 0, exif_transpose: bool = False):
         self.workers = max(1, int(workers))
         self.draft = check_draft(draft)  # the pipeline's jpeg_draft: every hand-over decodes under it
+        self.exif_transpose = bool(exif_transpose)  # and its exif_transpose: the containers are upright
         self._pool = None
         self._inline = False
 
@@ -325,11 +387,11 @@ class HostDecoder:
             self.start()
         if not self._inline:
             try:
-                return self._pool.submit(pillow_container, bytes(jpeg), self.draft)
+                return self._pool.submit(pillow_container, bytes(jpeg), self.draft, self.exif_transpose)
             except Exception as e:  # noqa: BLE001 - the pool broke after it started
                 self._fall_back(e)
         f = Future()
-        f.set_result(pillow_container(jpeg, self.draft))
+        f.set_result(pillow_container(jpeg, self.draft, self.exif_transpose))
         return f
 
     def close(self) -> None:

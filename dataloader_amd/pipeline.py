@@ -128,8 +128,16 @@ class MI355XAugPipeline:
                  multiscan_route: str = "auto", host_workers: int | None = None,
                  multiscan_host_max: int | None = None, prefetch: int | None = None,
                  start_host_pool: bool = False, side_ahead: int = 64, resample_filter=None,
-                 four_component: str = "host", png: str = "off", jpeg_draft: int = 0):
+                 four_component: str = "host", png: str = "off", jpeg_draft: int = 0,
+                 exif_transpose: bool = False):
         self._source = source
+        # EXIF orientation applied (ImageOps.exif_transpose before convert("RGB")): every slot and
+        # side context gets dino_ctx_set_exif_transpose and turns the JPEGs whose tag its walk
+        # verifies, the others (fallback.probe_orient: 255) join the hand-overs, and every
+        # hand-over applies the same call, so that a raw container is upright already (_orient)
+        self._exif = bool(exif_transpose)
+        if self._exif and not host_fallback:  # (the files the walk does not verify would decode unturned)
+            raise ValueError("exif_transpose=True needs host_fallback=True: Pillow decides the tags the device does not verify")
         # reduced-size JPEG decode (Pillow's draft("RGB", (N, N)), 0: off): every slot and side
         # context gets dino_ctx_set_draft and every hand-over decodes under the same draft, so a
         # batch is consistent whichever route an image took.  k_idct4 / k_color4 do not scale
@@ -170,7 +178,7 @@ class MI355XAugPipeline:
         self._side_hot = 0             # batches the look-ahead stays engaged for (see _pull_side)
         self._source_end = False
         workers = int(host_workers) if host_workers else min(8, os.cpu_count() or 1)
-        self._host = fallback.HostDecoder(workers, self._draft)
+        self._host = fallback.HostDecoder(workers, self._draft, self._exif)
         if start_host_pool:
             self._host.start()
         # "auto": the host takes a batch's coefficient-buffer images while its workers finish
@@ -181,6 +189,8 @@ class MI355XAugPipeline:
         # four_component: CMYK / YCCK images kept on the device (four_component="device")
         self.stats = {"batches": 0, "images": 0, "status": Counter(), "host_decoded": 0, "reserves": 0,
                       "side_decoded": 0, "four_component": 0, "png_device": 0, "png_host": 0}
+        if self._exif:  # images the contexts turned / images handed to Pillow because the walk verified nothing
+            self.stats.update(orient_device=0, orient_host=0)
         # host-side seconds per phase: pull / pack / probe (host half), wait (launch thread
         # waiting for the host half), launch (H2D copies + kernel enqueue)
         self.host_seconds = {"pull": 0.0, "pack": 0.0, "probe": 0.0, "wait": 0.0, "launch": 0.0}
@@ -243,6 +253,8 @@ class MI355XAugPipeline:
                 eng.set_png(True)
             if self._draft:
                 eng.set_draft(self._draft)
+            if self._exif:
+                eng.set_exif_transpose(True)
             self._slots.append(_Slot(eng))
         self._last: _Slot = self._slots[0]          # the last launched batch
         # output sets (shape key, tensors, consumer stream), batch n -> set n % (depth + 1)
@@ -427,6 +439,26 @@ class MI355XAugPipeline:
             self.stats["four_component"] += int(fallback.four_component_mask(info).sum())
         return fallback.accept_four_component(info)
 
+    def _orient(self, info: np.ndarray, ws: int, aws: int, cfg, ptrs, lens, count: bool = True, skip=(), tags=None):
+        """``_accept``'s info and the probe's workspace numbers as contexts with ``exif_transpose``
+        on decode the batch (``fallback.accept_orient``: upright sizes, the second RGB region of
+        each image that turns, the unverified files marked for Pillow), counted in ``stats`` once
+        per batch; ``aws`` becomes the sum of ``view_scratch_bound`` over the images as the views
+        see them.  ``skip``: images already handed over; ``tags``: the
+        ``probe_orient`` answer when the caller has it.  Returns (info, ws, aws, tags)."""
+        if not self._exif:
+            return info, ws, aws, None
+        tags = fallback.probe_orient(ptrs, lens) if tags is None else tags
+        o = tags.copy()
+        for i in skip:
+            o[int(i)] = 0
+        o[info[:, 0] != 0] = 0
+        if count:
+            self.stats["orient_host"] += int((o == fallback.ORIENT_UNVERIFIED).sum())
+            self.stats["orient_device"] += int(((o >= 2) & (o <= 8)).sum())
+        info, extra, extra_aws = fallback.accept_orient(info, o, cfg)
+        return info, ws + extra, aws + extra_aws, tags
+
     def _pull_raw(self) -> tuple:
         """The pull half of ``_prepare_next``: the source's next batch as (spans batch or None,
         JPEG list or None, pointers, lengths, references keeping the bytes alive)."""
@@ -458,9 +490,10 @@ class MI355XAugPipeline:
             cfg = self._cfg(*sizes)
             t1 = time.perf_counter()
             counted = False
+            tags = None
             if bs is not None and bs.registered:
                 info, ws, aws = fallback.probe_spans(ptrs, lens, self._max_image_dim, cfg)
-                info = self._accept(info)
+                info, ws, aws, tags = self._orient(self._accept(info), ws, aws, cfg, ptrs, lens)
                 counted = True
                 if not fallback.route_mask(info, self._host_fallback, self._route, self._host_max).any():
                     st = self._ring.acquire()
@@ -475,7 +508,8 @@ class MI355XAugPipeline:
                 st.fit(int(lens.sum()), B)
                 off, info, ws, aws = fallback.gather_probe(ptrs, lens, st.buf, self._gather_threads,
                                                            self._max_image_dim, cfg)
-                info = self._accept(info, count=not counted)
+                info, ws, aws, _ = self._orient(self._accept(info, count=not counted), ws, aws, cfg, ptrs, lens,
+                                                count=not counted, tags=tags)
                 st.off.numpy()[: B + 1] = off
                 hs["pack"] += time.perf_counter() - t1
                 if bs is not None:  # packed: the shard ranges are no longer read
@@ -515,7 +549,9 @@ class MI355XAugPipeline:
         fb = self._source.next_prepared(timeout=None if block else 0.0)
         if fb is None:
             return None
-        fb.info = self._accept(fb.info)
+        fb.info, fb.ws, fb.aws, _ = self._orient(self._accept(fb.info), fb.ws, fb.aws, self._cfg(*self._feed_sizes),
+                                                 fb.host + np.asarray(fb.offsets[:-1], np.int64),
+                                                 np.diff(np.asarray(fb.offsets, np.int64)))
         mask = fallback.route_mask(fb.info, self._host_fallback, self._route, self._host_max)
         if not mask.any():
             return _Prepared(None, None, fb.offsets, fb.info, fb.ws, fb.aws, self._feed_sizes, {}, feed=fb)
@@ -570,7 +606,8 @@ class MI355XAugPipeline:
             self._side = progside.DeviceSideDecoder(self.device, max_images=pool, max_image_dim=self._max_image_dim,
                                                     stream_set=self._stream_set, lanes=lanes,
                                                     four_component=self._four_component == "device",
-                                                    png=self._png == "device", draft=self._draft)
+                                                    png=self._png == "device", draft=self._draft,
+                                                    exif_transpose=self._exif)
             self.stats["side_lanes"] = lanes
         if pb.jpegs is not None:
             imgs = {int(i): pb.jpegs[i] for i in idx}
@@ -735,7 +772,7 @@ class MI355XAugPipeline:
         try:
             return f.result()
         except Exception:  # noqa: BLE001 - a broken worker pool: decode here (same bytes)
-            return fallback.pillow_container(jpeg, self._draft)
+            return fallback.pillow_container(jpeg, self._draft, self._exif)
 
     def _screen(self, sl: _Slot, pb: _Prepared, cfg, sizes) -> tuple[torch.Tensor, torch.Tensor, int, torch.Tensor | None]:
         """Collect a prepared batch's host decodes (re-packing the batch into its staging if
@@ -761,7 +798,8 @@ class MI355XAugPipeline:
             st.mask.numpy()[:B] = rm
             raw = st.mask[:B]
             pb.info, ws, aws = fallback.probe(st.buf.data_ptr(), off, B, self._max_image_dim, cfg, rm)
-            pb.info = self._accept(pb.info, count=False)
+            pb.info, ws, aws, _ = self._orient(self._accept(pb.info, count=False), ws, aws, cfg,
+                                               st.buf.data_ptr() + off[:-1], np.diff(off), count=False, skip=pb.futures)
             nbytes = int(off[-1])
         else:
             nbytes = int(pb.offsets[-1])

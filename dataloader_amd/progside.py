@@ -128,7 +128,7 @@ class _SideEngine:
 
     def __init__(self, device: torch.device, max_images: int, max_image_dim: int, cu_count: int = 0,
                  dedicated: bool = True, index: int = 0, stream_set: int = 0, lanes: bool = False,
-                 four_component: bool = False, png: bool = False, draft: int = 0):
+                 four_component: bool = False, png: bool = False, draft: int = 0, exif_transpose: bool = False):
         self.raw = _create_stream(device.index or 0, int(cu_count)) if dedicated else None
         self.stream = self.raw if dedicated else role_stream(device, "side", index, stream_set)
         self.eng = IngestEngine(device, max_batch=max_images, max_views=1, max_crop_size=8,
@@ -140,6 +140,8 @@ class _SideEngine:
             self.eng.set_png(True)
         if draft:  # the containers then hold the scaled images, as the batches' own contexts decode them
             self.eng.set_draft(draft)
+        if exif_transpose:  # the containers then hold the upright images, which the batches' contexts do not turn again
+            self.eng.set_exif_transpose(True)
         self.copy = role_stream(device, "side_copy", index, stream_set)  # this context's torch stream (allocations, copies)
         self.last: torch.cuda.Event | None = None   # the engine's workspace is free once this completes
         self.keep = None                             # host / device inputs of the mini-batch in flight
@@ -199,7 +201,7 @@ class DeviceSideDecoder:
 
     def __init__(self, device: torch.device, max_images: int = WAVE_POOL, min_images: int | None = None,
                  engines: int | None = None, max_image_dim: int = 0, stream_set: int = 0, lanes: bool = False,
-                 four_component: bool = False, png: bool = False, draft: int = 0):
+                 four_component: bool = False, png: bool = False, draft: int = 0, exif_transpose: bool = False):
         import os
         # measured (scripts/route_study.py, 16 progressive per 256-image batch, dedicated queues,
         # look-ahead 64, profiles/r03_side_pools.jsonl): pools of 16 images on 2 contexts 11.2k img/s,
@@ -223,6 +225,7 @@ class DeviceSideDecoder:
         self.four_component = bool(four_component)  # the side contexts decode CMYK / YCCK files
         self.png = bool(png)                        # and the PNG files the device takes
         self.draft = int(draft)                     # the pipeline's jpeg_draft (the probe's sizes are then upper bounds)
+        self.exif_transpose = bool(exif_transpose)  # the pipeline's exif_transpose
         self.lane_min = int(os.environ.get("DINO_SIDE_LANE_MIN", LANE_MIN_POOL))  # smaller pools: wave decoder
         self._engines: list[_SideEngine] = []
         self._rr = 0
@@ -269,7 +272,8 @@ class DeviceSideDecoder:
         if len(self._engines) < self.cap:
             e = _SideEngine(self.device, self.max_images, self.max_image_dim, self.cu_count, self.dedicated,
                             index=len(self._engines), stream_set=self.stream_set, lanes=self.lanes,
-                            four_component=self.four_component, png=self.png, draft=self.draft)
+                            four_component=self.four_component, png=self.png, draft=self.draft,
+                            exif_transpose=self.exif_transpose)
             self._engines.append(e)
             return e
         e = self._engines[self._rr % len(self._engines)]
@@ -326,6 +330,10 @@ class DeviceSideDecoder:
             info = fallback.accept_four_component(info)
         if self.png:
             info = fallback.accept_png(info, "device")
+        if self.exif_transpose:  # the second RGB region of each image the context turns (upright sizes in info)
+            o = off.numpy()
+            info, extra, _ = fallback.accept_orient(info, fallback.probe_orient(hb.data_ptr() + o[:-1], np.diff(o)))
+            ws += extra
         t3 = time.perf_counter()
         ph["probe"] += t3 - t2
         eng.reserve(ws, 0)

@@ -34,8 +34,10 @@ class MI355XUserAugPipeline:
 
     def __init__(self, source: Any, spec, batch_size: int, out_dtype="bf16", device: int = 0,
                  max_image_dim: int = 0, workspace_bytes: int = 0, norm=None, resample_filter=None,
-                 png: str = "off", jpeg_draft: int = 0):
+                 png: str = "off", jpeg_draft: int = 0, exif_transpose: bool = False):
         self._source = source
+        # EXIF orientation applied: on the context, and by Pillow for the files it does not verify
+        self._exif = bool(exif_transpose)
         # reduced-size JPEG decode (Pillow's draft("RGB", (N, N))): on the context and in the hand-overs
         self._draft = fallback.check_draft(jpeg_draft)
         # PNG files: "off" leaves them zero-filled; "host" and "device" both hand every PNG Pillow may
@@ -53,6 +55,8 @@ class MI355XUserAugPipeline:
             self._engine.set_resample_filter(resample_filter)
         if self._draft:
             self._engine.set_draft(self._draft)
+        if self._exif:
+            self._engine.set_exif_transpose(True)
         self.stats = {"batches": 0, "images": 0, "status": Counter(), "host_decoded": 0}
         self._pending_status: deque = deque()
         self._closed = False
@@ -89,14 +93,19 @@ class MI355XUserAugPipeline:
         info, ws, _ = fallback.probe(host_buf.data_ptr(), offsets.numpy(), len(jpegs), self._max_image_dim)
         raw = None
         png = "off" if self._png == "off" else "host"
+        orient = fallback.probe_orient_list(jpegs) if self._exif else np.zeros(len(jpegs), np.uint8)
+        info, extra, _ = fallback.accept_orient(info, orient)  # (unverified tags: handed over below)
         if np.isin(info[:, 0], (fallback.IMG_UNSUPPORTED, fallback.IMG_LIMIT)).any() or \
                 (png != "off" and fallback.png_mask(info).any()):
-            jpegs, n, rm = fallback.hand_over(list(jpegs), info[:, 0], kind=info[:, 3], png=png, draft=self._draft)
+            jpegs, n, rm = fallback.hand_over(list(jpegs), info[:, 0], kind=info[:, 3], png=png, draft=self._draft,
+                                              exif_transpose=self._exif)
             self.stats["host_decoded"] += n
             host_buf, offsets = pack_jpegs(jpegs, pin=True)
             info, ws, _ = fallback.probe(host_buf.data_ptr(), offsets.numpy(), len(jpegs), self._max_image_dim,
                                          raw_mask=rm)
+            info, extra, _ = fallback.accept_orient(info, np.where(rm != 0, 0, orient))
             raw = torch.from_numpy(rm).pin_memory()
+        ws += extra
         ds = int(self._spec.decode_size)
         if self._draft:  # the probe reports coded sizes: the JPEGs the context decodes come out scaled
             info = info.copy()

@@ -53,7 +53,9 @@
  *    probes' info, dino_kernel_times id 23, dino_debug_region 10 and 11; dino_host_alloc /
  *    dino_host_free (page-locked memory for hosts where a mapping cannot be registered);
  *    dino_ctx_set_draft (JPEGs decoded at Pillow's Image.draft size, off by default) and
- *    dino_kernel_times ids 24 to 26.
+ *    dino_kernel_times ids 24 to 26; dino_ctx_set_exif_transpose (JPEGs leave the decode as
+ *    ImageOps.exif_transpose gives them, off by default), dino_probe_orient, dino_orient_map,
+ *    dino_orient_tile and dino_kernel_times ids 27 and 28.
  */
 #ifndef DINO_INGEST_H
 #define DINO_INGEST_H
@@ -394,6 +396,36 @@ int dino_ctx_set_png(dino_ctx* ctx, int32_t on);
  * ("k_color_red") time its kernels.  What a damaged stream's out-of-range coefficients give at
  * reduced size is not pinned against Pillow. */
 int dino_ctx_set_draft(dino_ctx* ctx, int32_t n);
+
+/* EXIF orientation on this ctx, from the next call on: on = 0 (default) decodes every image as
+ *   Image.open(..).convert("RGB")
+ * does, the Orientation tag ignored; on != 0 as
+ *   ImageOps.exif_transpose(Image.open(..)).convert("RGB")
+ * does (after im.draft under dino_ctx_set_draft), for every JPEG whose tag the device's walk
+ * verifies: exactly one APP1 "Exif\0\0" segment before the first SOS, a plain TIFF header, IFD0
+ * inside the segment, one Orientation entry of type SHORT, count 1 and value 1..8.
+ * dino_batch_info, dino_copy_rgb*, the view records and the views then refer to the upright
+ * image: width and height are swapped for orientations 5..8.  Every other file decodes unturned:
+ * dino_probe_orient tells the caller which of them Pillow has to decide (255), and a caller that
+ * hands images over applies exif_transpose on the host; raw containers are taken as upright.  An
+ * image that turns needs a second RGB region in the decode workspace: the probes have no ctx and
+ * do not count it, the caller adds align256(align16(3 w h + 16)) bytes for each image with
+ * orientation 2..8 before dino_reserve, and sizes the augment workspace from the upright width and
+ * height (dino_augment_need on the swapped info).  dino_kernel_times ids 27 ("k_exif": the tag
+ * walk, the tile scan and the descriptor update) and 28 ("k_orient") time its kernels. */
+int dino_ctx_set_exif_transpose(dino_ctx* ctx, int32_t on);
+
+/* The device's orientation walk on the host (no GPU involved): out[i] = 0 where image i stays as
+ * it is for a ctx with dino_ctx_set_exif_transpose on (no tag, value 1, not a JPEG), 2..8 where
+ * the ctx turns it, 255 where the walk verifies neither and Pillow decides (a second Exif
+ * segment, an entry of another type or count or a value outside 1..8, an IFD that leaves its
+ * segment, any XMP packet when EXIF gave no orientation).  ptrs: absolute host addresses. */
+int dino_probe_orient(const uint64_t* ptrs, const int64_t* lens, int32_t batch, uint8_t* out);
+
+/* Where orientation 1..8 sends pixel (x, y) of a w x h image (the mapping k_orient applies; the
+ * upright image is h x w for 5..8), and the side of the square tiles k_orient works in. */
+int dino_orient_map(int32_t orientation, int32_t w, int32_t h, int32_t x, int32_t y, int32_t* ox, int32_t* oy);
+int dino_orient_tile(void);
 
 /* The coefficient code of the resample kernels run on the host (no GPU involved; tests and
  * introspection): for in_size -> out_size with `filter`, *ksize = taps reserved per output;
