@@ -123,7 +123,7 @@ class MI355XBackend:
                  hbm_fraction: float = 0.15, host_workers: int | None = None, multiscan_route: str = "side",
                  side_ahead: int | None = None, resample_filter: str | None = None,
                  four_component: str = "host", png: str = "off", jpeg_draft: int = 0,
-                 exif_transpose: bool = False) -> None:
+                 exif_transpose: bool = False, png_forms: str = "plain") -> None:
         # Pillow filter of every resize: None = bicubic everywhere (CPUBackend parity, which
         # ignores EvalAugSpec.interpolation too); a filter's name applies to every recipe;
         # "spec" honours EvalAugSpec.interpolation as the reference's GPU peer does
@@ -147,6 +147,12 @@ class MI355XBackend:
         if png not in ("off", "host", "device"):
             raise ValueError(f"png must be 'off', 'host' or 'device', not {png!r}")
         self._png = png
+        # "plain" (default): png="device" decodes 8-bit files without interlace and hands the other
+        # forms to Pillow; "all": bit depths 1 / 2 / 4 / 16 and Adam7 stay on the device too
+        # (k_unfilter_forms).  The UserAugSpec pipeline hands every PNG over whatever this says
+        from .fallback import check_png_forms
+        check_png_forms(png_forms, png)
+        self._png_forms = png_forms
         # reduced-size JPEG decode, off at 0: N > 0 decodes every JPEG as Pillow does after
         # im.draft("RGB", (N, N)) (1/2, 1/4 or 1/8 of the coded size where both sides stay >= N;
         # fallback.draft_scale), on the device (libjpeg's reduced inverse DCTs) and in every
@@ -318,6 +324,7 @@ class MI355XBackend:
             png=self._png,
             jpeg_draft=self._jpeg_draft,
             exif_transpose=self._exif_transpose,
+            png_forms=self._png_forms,
         )
 
     def build_pipeline_iterator(self, pipeline: Any, aug_spec: Any, output_map: list[str],

@@ -19,6 +19,7 @@
 
 #include "exif_parse.hpp"
 #include "hostcopy.hpp"
+#include "inflate.hpp"
 #include "jpeg_parse.hpp"
 #include "kernels.hpp"
 #include "mask.hpp"
@@ -66,6 +67,7 @@ struct dino_ctx {
   int32_t filter = kBicubic;  // dino_ctx_set_resample_filter: read at each augment / resize launch
   int32_t four_component = 0; // dino_ctx_set_four_component: read at each decode launch
   int32_t png = 0;            // dino_ctx_set_png: read at each decode launch
+  int32_t png_forms = 0;      // dino_ctx_set_png_forms: read at each decode launch
   int32_t draft = 0;          // dino_ctx_set_draft: read at each decode launch
   int32_t exif_transpose = 0; // dino_ctx_set_exif_transpose: read at each decode launch
   OCtl* d_octl = nullptr;     // k_orient's tiles (allocated by the first dino_ctx_set_exif_transpose(ctx, 1))
@@ -154,7 +156,7 @@ int dino_decode_spans(dino_ctx* c, const uint8_t* d_bytes, const int64_t* d_offs
     return fail(DINO_EINVAL, "dino_decode: batch %s%lld exceeds ctx max_batch", "", batch);
   hipStream_t s = (hipStream_t)stream;
   DecodeArgs a{d_bytes, d_offsets, d_lengths, d_raw_mask, batch, c->lim.max_image_dim, c->d_desc, c->d_ws,
-               c->ws_size, c->geom, c->d_pctl, c->four_component, c->png, c->draft,
+               c->ws_size, c->geom, c->d_pctl, c->four_component, c->png, c->png && c->png_forms, c->draft,
                c->exif_transpose ? c->d_octl : nullptr};
   hipError_t e = launch_decode(a, s, c->tm());
   if (e != hipSuccess) return hip_fail(e, "dino_decode");
@@ -591,6 +593,104 @@ int dino_ctx_set_png(dino_ctx* c, int32_t on) {
   return DINO_OK;
 }
 
+int dino_ctx_set_png_forms(dino_ctx* c, int32_t on) {
+  if (!c) return fail(DINO_EINVAL, "dino_ctx_set_png_forms: null ctx%s%lld");
+  if (on && !c->png) return fail(DINO_EINVAL, "dino_ctx_set_png_forms: needs dino_ctx_set_png on%s%lld");
+  c->png_forms = on != 0;  // read at each launch (launch_decode), where it holds only beside png
+  return DINO_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// The descriptor a context with dino_ctx_set_png and dino_ctx_set_png_forms on gives the file after
+// k_pnghead, k_pnghead_forms and the walk of k_pngwalk; true when it is an extended form it decodes.
+bool png_forms_head(const uint8_t* p, int64_t len, int32_t max_image_dim, ImgDesc* d, PngWalk* w) {
+  if (max_image_dim <= 0 || max_image_dim > kMaxImageDim) max_image_dim = kMaxImageDim;
+  d->kind = 0;
+  d->width = d->height = 0;
+  d->coef_bytes = 0;
+  if (parse_png_head(p, len, max_image_dim, d) != kPngDecline) return false;
+  if (parse_png_forms_head(p, len, d) != DINO_IMG_OK) return false;
+  d->status = png_walk(p, len, d->color, w);
+  return d->status != kPngDecline;  // (OK, or CORRUPT: Pillow raises and so does the device)
+}
+
+// inflate.hpp with one lane.
+struct HostInfIO {
+  int lane = 0, nl = 1;
+  const uint8_t* z;
+  int64_t zn;
+  uint8_t* out;
+  int64_t out_cap;
+  uint8_t* win;
+  InfTab *lt, *dt;
+  uint8_t* lens;
+  void sync() {}
+  uint32_t in(int64_t i) const { return i >= 0 && i < zn ? z[i] : 0u; }
+  void flush(int64_t at, int n) {
+    for (int i = 0; i < n; ++i)
+      if (at + i < out_cap) out[at + i] = win[(at + i) & (kInfWin - 1)];
+  }
+};
+}  // namespace
+
+extern "C" {
+
+int dino_probe_png_forms(const uint64_t* ptrs, const int64_t* lens, int32_t batch, int32_t max_image_dim, uint8_t* form,
+                         int64_t* ws_need) {
+  if (batch < 0 || (batch > 0 && (!ptrs || !lens || !form || !ws_need)))
+    return fail(DINO_EINVAL, "dino_probe_png_forms: bad arguments%s%lld");
+  for (int32_t i = 0; i < batch; ++i) {
+    ImgDesc d;
+    PngWalk w;
+    form[i] = 0;
+    ws_need[i] = 0;
+    if (lens[i] <= 0 || !png_forms_head((const uint8_t*)(uintptr_t)ptrs[i], lens[i], max_image_dim, &d, &w)) continue;
+    if (d.status != DINO_IMG_OK) continue;  // Pillow raises on it: kind -1 of dino_probe, zeros
+    form[i] = 1;
+    ws_need[i] = image_chunk_bytes(d).total();
+  }
+  return DINO_OK;
+}
+
+int dino_debug_png_forms_decode(const uint8_t* p, int64_t len, int32_t max_image_dim, uint8_t* rgb, int64_t rgb_cap,
+                                int32_t* info, int64_t* layout) {
+  if (!p || len <= 0 || !info || !layout || (!rgb && rgb_cap > 0))
+    return fail(DINO_EINVAL, "dino_debug_png_forms_decode: bad arguments%s%lld");
+  ImgDesc d;
+  PngWalk w;
+  info[0] = DINO_IMG_CORRUPT, info[1] = info[2] = info[3] = 0;
+  for (int k = 0; k < 8; ++k) layout[k] = 0;
+  if (!png_forms_head(p, len, max_image_dim, &d, &w)) return DINO_OK;
+  info[0] = d.status, info[1] = d.width, info[2] = d.height, info[3] = 1;
+  if (d.status != DINO_IMG_OK) return DINO_OK;
+  const ChunkSizes z = image_chunk_bytes(d);
+  const PngForm f = png_form_of(d);
+  layout[0] = z.total(), layout[1] = z.ent, layout[2] = z.coef, layout[3] = z.plane, layout[4] = z.htab, layout[5] = z.rgb;
+  layout[6] = png_inflated_bytes(d), layout[7] = png_form_geom(f).rows;
+  if ((int64_t)d.width * d.height * 3 > rgb_cap) return (info[0] = DINO_IMG_NO_SPACE, DINO_OK);
+  std::vector<uint8_t> zs((size_t)w.idat_bytes + 1), inf((size_t)layout[6] + 1), win(kInfWin), cl(kInfMaxLens);
+  int64_t pos = w.idat_off, zn = 0;
+  for (int c = 0; c < w.idat_chunks; ++c) {
+    const uint32_t n = rd32be(p + pos);
+    memcpy(zs.data() + zn, p + pos + 8, n);
+    zn += n;
+    pos += 12 + (int64_t)n;
+  }
+  InfTab lt, dt;
+  HostInfIO io;
+  io.z = zs.data(), io.zn = zn, io.out = inf.data(), io.out_cap = layout[6], io.win = win.data(), io.lt = &lt, io.dt = &dt,
+  io.lens = cl.data();
+  Inflater<HostInfIO> run(io, zn, layout[6]);
+  if ((info[0] = run.run()) != DINO_IMG_OK) return DINO_OK;
+  uint8_t pal[768];
+  memset(pal, 0, sizeof(pal));
+  if (w.plte_off) memcpy(pal, p + w.plte_off, w.plte_n);
+  if (!png_forms_unfilter_rows(inf.data(), f, pal, rgb)) info[0] = DINO_IMG_CORRUPT;
+  return DINO_OK;
+}
+
 int dino_ctx_set_draft(dino_ctx* c, int32_t n) {
   if (!c) return fail(DINO_EINVAL, "dino_ctx_set_draft: null ctx%s%lld");
   if (n < 0) return fail(DINO_EINVAL, "dino_ctx_set_draft: negative size%s %lld", "", (long long)n);
@@ -722,7 +822,7 @@ int dino_debug_region(dino_ctx* c, int32_t index, int32_t region, void* d_dst, i
       break;
     case 11:  // kind 4: the inflated, still-filtered rows (k_inflate)
       src = c->d_ws + d.plane_off;
-      n = d.kind == 4 ? (int64_t)d.height * (1 + (int64_t)d.width * d.max_h) : 0;
+      n = d.kind == 4 ? png_inflated_bytes(d) : 0;
       break;
     default: return fail(DINO_EINVAL, "dino_debug_region: region %s%lld", "", region);
   }

@@ -28,6 +28,7 @@
 //   kernels_small.inc               k_masks (iBOT), k_bf16_to_fp8 (Stage 5), k_copy_rgb*, k_info
 //   kernels_timer.inc               host: KernelTimer, DINO_SYNC_CHECK
 //   kernels_png.inc                 k_pnghead, k_pngwalk, k_inflate, k_unfilter (opt-in)
+//   kernels_png_forms.inc           k_pnghead_forms, k_unfilter_forms: depths 1 / 2 / 4 / 16 and Adam7 (opt-in)
 //   kernels_draft.inc               k_draft, k_idct_red, k_color_red: reduced-size JPEG decode (opt-in)
 //   kernels_orient.inc              k_exif, k_orient_scan, k_orient, k_orient_done: EXIF orientation applied (opt-in)
 //   kernels_launch.inc              host: init_launch_geom and every launch_*; k_pixel_ops
@@ -47,6 +48,7 @@
 #include "progressive.hpp"
 #include "pscan.hpp"
 #include "png_parse.hpp"
+#include "png_forms.hpp"
 #include "inflate.hpp"
 #include "sampler.hpp"
 
@@ -3515,6 +3517,7 @@ __global__ void __launch_bounds__(kVFinalThreads) k_vfinal(const ImgDesc* __rest
 #include "kernels_small.inc"
 #include "kernels_timer.inc"
 #include "kernels_png.inc"
+#include "kernels_png_forms.inc"
 #include "kernels_draft.inc"
 #include "kernels_orient.inc"
 #include "kernels_launch.inc"

@@ -103,6 +103,8 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
                                                   a.desc)));
   // a context with dino_ctx_set_png on: PNG files get their descriptor before the plan
   if (a.png) TIMED(tm, kKPng, s, (k_pnghead<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.max_dim, a.desc)));
+  // a context with dino_ctx_set_png_forms on: the files k_pnghead declined for depth or interlace alone get theirs
+  if (a.png && a.png_forms) TIMED(tm, kKPng, s, (k_pnghead_forms<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.desc)));
   // a context with dino_ctx_set_draft on: the JPEGs that scale get their reduced size before the plan
   if (a.draft > 0) TIMED(tm, kKDraft, s, (k_draft<<<(B + 63) / 64, 64, 0, s>>>(a.desc, B, a.draft)));
   // a context with dino_ctx_set_exif_transpose on: every image gets its orientation before the plan
@@ -146,6 +148,7 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
     TIMED(tm, kKPng, s, (k_pngwalk<<<B, kPngWalkThreads, 0, s>>>(a.bytes, a.offsets, a.lengths, a.desc, a.ws, a.pctl)));
     TIMED(tm, kKPng, s, (k_inflate<<<min(B, a.geom.grid_inf), 64, 0, s>>>(a.desc, a.ws, a.pctl, B)));
     TIMED(tm, kKPng, s, (k_unfilter<<<B, 64, 0, s>>>(a.desc, a.ws)));
+    if (a.png_forms) TIMED(tm, kKPng, s, (k_unfilter_forms<<<B, 64, 0, s>>>(a.desc, a.ws)));
   }
   if (a.octl) {  // after every colour stage: the images k_exif tagged turn, then show their upright side
     TIMED(tm, kKOrient, s, (k_orient<<<a.geom.grid_or, 256, 0, s>>>(a.desc, a.ws, a.octl, B)));

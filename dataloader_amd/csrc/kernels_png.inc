@@ -154,6 +154,7 @@ __global__ void __launch_bounds__(64) k_inflate(ImgDesc* __restrict__ desc, uint
 __global__ void __launch_bounds__(64) k_unfilter(ImgDesc* __restrict__ desc, uint8_t* __restrict__ ws) {
   ImgDesc& d = desc[blockIdx.x];
   if (d.status != DINO_IMG_OK || d.kind != kPngKind) return;
+  if (d.coef_bytes != 0) return;  // an extended form (png_forms.hpp): k_unfilter_forms' image
   const int W = d.width, H = d.height, bpp = d.max_h, color = d.color, lane = threadIdx.x;
   const int64_t stride = 1 + (int64_t)W * bpp;
   const uint8_t* inf = ws + d.plane_off;

@@ -6,6 +6,7 @@
 #include "kernels.hpp"
 #include "progressive.hpp"
 #include "png_parse.hpp"
+#include "png_forms.hpp"
 #include "pscan.hpp"
 #include "lscan.hpp"
 #include "resize.hpp"
@@ -103,6 +104,7 @@ DHD ChunkSizes image_chunk_bytes(const ImgDesc& d) {
   if (kPng && d.kind == kPngKind) {  // the joined zlib stream, one carried row, the filtered rows, the palette
     z.ent = align16((int64_t)d.scan_len + 64);
     z.coef = align16((int64_t)d.width * 4 + 16);
+    if (png_is_form(d)) z.coef = align16(8 * png_form_max_units(d) + 16);  // (k_unfilter_forms: 8 bytes a unit)
     z.plane = align16(png_inflated_bytes(d) + 64);
     z.htab = kPngPalBytes;
     return chunk_finish(z);

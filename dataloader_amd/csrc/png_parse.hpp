@@ -60,7 +60,10 @@ DHD int png_channels(int color) {
 }
 
 // Bytes of the inflated stream Pillow's decoder consumes: H rows of a filter byte and W pixels.
-DHD int64_t png_inflated_bytes(const ImgDesc& d) { return (int64_t)d.height * (1 + (int64_t)d.width * d.max_h); }
+// An extended form (png_forms.hpp) states its own in coef_bytes, which parse_png_head leaves 0.
+DHD int64_t png_inflated_bytes(const ImgDesc& d) {
+  return d.coef_bytes ? d.coef_bytes : (int64_t)d.height * (1 + (int64_t)d.width * d.max_h);
+}
 
 // Signature and IHDR fields (no CRC: png_walk checks it).  A kind-4 descriptor keeps the PNG's
 // own numbers in fields the JPEG stages of a kind-4 image never read: color = colour type,

@@ -88,6 +88,7 @@ class IngestEngine:
         self.resample_filter = 0  # set_resample_filter's choice (DINO_FILTER_*; 0: bicubic)
         self.four_component = False  # set_four_component's choice (False: CMYK / YCCK files report status 1)
         self.png = False  # set_png's choice (False: PNG files report status -1, as any non-JPEG)
+        self.png_forms = False  # set_png_forms's choice (False: depths 1 / 2 / 4 / 16 and Adam7 report status 1)
         self.draft = 0  # set_draft's choice (0: every JPEG decodes at its coded size)
         self.exif_transpose = False  # set_exif_transpose's choice (False: the Orientation tag is ignored)
 
@@ -176,6 +177,15 @@ class IngestEngine:
         ``DINO_IMG_CORRUPT`` (``False``, the default) from the next call on (``dino_ctx_set_png``)."""
         _lib.check(self.lib.dino_ctx_set_png(self._ctx, int(bool(on))), "dino_ctx_set_png")
         self.png = bool(on)
+
+    def set_png_forms(self, on: bool) -> None:
+        """Also decode the PNG forms ``set_png`` leaves out (bit depths 1, 2, 4 and 16, Adam7
+        interlace) on this context (``True``), or report them ``DINO_IMG_UNSUPPORTED`` (``False``,
+        the default), from the next call on (``dino_ctx_set_png_forms``; an error unless
+        ``set_png(True)`` came first).  The probes keep reporting these files as declined:
+        ``fallback.probe_png_forms`` names them and their workspace bytes."""
+        _lib.check(self.lib.dino_ctx_set_png_forms(self._ctx, int(bool(on))), "dino_ctx_set_png_forms")
+        self.png_forms = bool(on)
 
     def set_draft(self, n: int) -> None:
         """Decode this context's JPEGs of one or three components at the size of Pillow's

@@ -78,6 +78,52 @@ def accept_png(info: np.ndarray, png: str = "device") -> np.ndarray:
     return out
 
 
+PNG_FORMS = ("plain", "all")
+
+
+def check_png_forms(forms: str, png: str) -> None:
+    if forms not in PNG_FORMS:
+        raise ValueError(f"png_forms must be 'plain' or 'all', not {forms!r}")
+    if forms == "all" and png != "device":
+        raise ValueError("png_forms='all' needs png='device': the other modes decode no PNG on the device")
+
+
+def probe_png_forms(ptrs: np.ndarray, lens: np.ndarray, max_image_dim: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """``dino_probe_png_forms`` over images where they lie (absolute host addresses + lengths) ->
+    (form int32[B, 3], ws int64[B]).  ``form[:, 0]`` is 1 where a context with
+    ``dino_ctx_set_png_forms`` on decodes a PNG the probes report as kind 5 (bit depth 1, 2, 4 or
+    16, Adam7), with the image's width and height from IHDR in columns 1 and 2 and its
+    decode-workspace bytes in ``ws``; 0 everywhere else."""
+    p = np.ascontiguousarray(ptrs, np.uint64)
+    n = np.ascontiguousarray(lens, np.int64)
+    flag = np.zeros(len(p), np.uint8)
+    ws = np.zeros(len(p), np.int64)
+    _lib.check(_lib.load().dino_probe_png_forms(p.ctypes.data_as(ctypes.c_void_p), n.ctypes.data_as(ctypes.c_void_p),
+                                                len(p), int(max_image_dim), flag.ctypes.data_as(ctypes.c_void_p),
+                                                ws.ctypes.data_as(ctypes.c_void_p)), "dino_probe_png_forms")
+    form = np.zeros((len(p), 3), np.int32)
+    form[:, 0] = flag
+    for i in np.flatnonzero(flag):  # (IHDR: width and height at bytes 16..24, verified by the probe)
+        form[i, 1:] = np.frombuffer(ctypes.string_at(int(p[i]) + 16, 8), ">u4")
+    return form, ws
+
+
+def accept_png_forms(info: np.ndarray, form: np.ndarray, ws: np.ndarray, cfg=None) -> tuple[np.ndarray, int, int]:
+    """The probe's info (before or after ``accept_png``) as contexts with
+    ``dino_ctx_set_png_forms`` on decode the batch: kind-5 rows with ``form[:, 0] == 1`` become
+    status 0, kind 1 with their width and height, as ``accept_png`` does for kind 4.  Returns
+    (a copy of info, decode-workspace bytes to add, augment-workspace bytes to add): the probe
+    counted neither for kind 5; the last is ``augment_need`` of those rows for ``cfg`` (0 without)."""
+    out = np.array(info, np.int32, copy=True)
+    form = np.asarray(form)
+    m = (out[:, 3] == KIND_PNG_DECLINED) & np.isin(out[:, 0], (IMG_CORRUPT, IMG_UNSUPPORTED)) & (form[:, 0] == 1)
+    out[m, 0] = 0
+    out[m, 1:3] = form[m, 1:3]
+    out[m, 3] = KIND_MULTISCAN
+    aws = augment_need(out[m], cfg) if cfg is not None and m.any() else 0
+    return out, int(np.asarray(ws, np.int64)[m].sum()), aws
+
+
 def four_component_mask(info: np.ndarray) -> np.ndarray:
     """Rows of a probed batch that are four-component (CMYK / YCCK) files a context with
     ``dino_ctx_set_four_component`` on decodes (status 1, kind 3)."""

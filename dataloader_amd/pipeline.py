@@ -129,7 +129,7 @@ class MI355XAugPipeline:
                  multiscan_host_max: int | None = None, prefetch: int | None = None,
                  start_host_pool: bool = False, side_ahead: int = 64, resample_filter=None,
                  four_component: str = "host", png: str = "off", jpeg_draft: int = 0,
-                 exif_transpose: bool = False):
+                 exif_transpose: bool = False, png_forms: str = "plain"):
         self._source = source
         # EXIF orientation applied (ImageOps.exif_transpose before convert("RGB")): every slot and
         # side context gets dino_ctx_set_exif_transpose and turns the JPEGs whose tag its walk
@@ -149,6 +149,10 @@ class MI355XAugPipeline:
         # dino_ctx_set_png) and hands the rest to Pillow (fallback.accept_png)
         fallback.check_png(png)
         self._png = png
+        # "all": the contexts also decode bit depths 1 / 2 / 4 / 16 and Adam7 (dino_ctx_set_png_forms);
+        # the probes keep reporting those files as declined, fallback.accept_png_forms takes them back (_forms)
+        fallback.check_png_forms(png_forms, png)
+        self._png_forms = png_forms == "all"
         self._aug_cfg = aug_cfg
         # four-component (CMYK / YCCK) JPEGs: "host" hands them to Pillow, "device" decodes them in
         # the kernels (every slot and side context gets dino_ctx_set_four_component) and routes them
@@ -251,6 +255,8 @@ class MI355XAugPipeline:
                 eng.set_four_component(True)
             if self._png == "device":
                 eng.set_png(True)
+            if self._png_forms:
+                eng.set_png_forms(True)
             if self._draft:
                 eng.set_draft(self._draft)
             if self._exif:
@@ -439,6 +445,24 @@ class MI355XAugPipeline:
             self.stats["four_component"] += int(fallback.four_component_mask(info).sum())
         return fallback.accept_four_component(info)
 
+    def _forms(self, info: np.ndarray, ws: int, aws: int, cfg, ptrs, lens, count: bool = True, skip=()):
+        """``_accept``'s info and the probe's workspace numbers as contexts with ``png_forms="all"``
+        decode the batch (``fallback.accept_png_forms``: the declined PNGs of the extended forms
+        become coefficient-buffer images, their workspace and view scratch added), moved from
+        ``png_host`` to ``png_device`` in ``stats`` once per batch.  ``skip``: images already
+        handed over.  Returns (info, ws, aws)."""
+        if not self._png_forms or not (info[:, 3] == fallback.KIND_PNG_DECLINED).any():
+            return info, ws, aws
+        form, need = fallback.probe_png_forms(ptrs, lens, self._max_image_dim)
+        for i in skip:
+            form[int(i), 0] = 0
+        info, extra, extra_aws = fallback.accept_png_forms(info, form, need, cfg)
+        if count:
+            n = int(((form[:, 0] == 1) & (info[:, 0] == 0)).sum())
+            self.stats["png_device"] += n
+            self.stats["png_host"] -= n
+        return info, ws + extra, aws + extra_aws
+
     def _orient(self, info: np.ndarray, ws: int, aws: int, cfg, ptrs, lens, count: bool = True, skip=(), tags=None):
         """``_accept``'s info and the probe's workspace numbers as contexts with ``exif_transpose``
         on decode the batch (``fallback.accept_orient``: upright sizes, the second RGB region of
@@ -493,7 +517,8 @@ class MI355XAugPipeline:
             tags = None
             if bs is not None and bs.registered:
                 info, ws, aws = fallback.probe_spans(ptrs, lens, self._max_image_dim, cfg)
-                info, ws, aws, tags = self._orient(self._accept(info), ws, aws, cfg, ptrs, lens)
+                info, ws, aws = self._forms(self._accept(info), ws, aws, cfg, ptrs, lens)
+                info, ws, aws, tags = self._orient(info, ws, aws, cfg, ptrs, lens)
                 counted = True
                 if not fallback.route_mask(info, self._host_fallback, self._route, self._host_max).any():
                     st = self._ring.acquire()
@@ -508,8 +533,9 @@ class MI355XAugPipeline:
                 st.fit(int(lens.sum()), B)
                 off, info, ws, aws = fallback.gather_probe(ptrs, lens, st.buf, self._gather_threads,
                                                            self._max_image_dim, cfg)
-                info, ws, aws, _ = self._orient(self._accept(info, count=not counted), ws, aws, cfg, ptrs, lens,
-                                                count=not counted, tags=tags)
+                info, ws, aws = self._forms(self._accept(info, count=not counted), ws, aws, cfg, ptrs, lens,
+                                            count=not counted)
+                info, ws, aws, _ = self._orient(info, ws, aws, cfg, ptrs, lens, count=not counted, tags=tags)
                 st.off.numpy()[: B + 1] = off
                 hs["pack"] += time.perf_counter() - t1
                 if bs is not None:  # packed: the shard ranges are no longer read
@@ -607,7 +633,7 @@ class MI355XAugPipeline:
                                                     stream_set=self._stream_set, lanes=lanes,
                                                     four_component=self._four_component == "device",
                                                     png=self._png == "device", draft=self._draft,
-                                                    exif_transpose=self._exif)
+                                                    exif_transpose=self._exif, png_forms=self._png_forms)
             self.stats["side_lanes"] = lanes
         if pb.jpegs is not None:
             imgs = {int(i): pb.jpegs[i] for i in idx}
@@ -798,7 +824,9 @@ class MI355XAugPipeline:
             st.mask.numpy()[:B] = rm
             raw = st.mask[:B]
             pb.info, ws, aws = fallback.probe(st.buf.data_ptr(), off, B, self._max_image_dim, cfg, rm)
-            pb.info, ws, aws, _ = self._orient(self._accept(pb.info, count=False), ws, aws, cfg,
+            pb.info, ws, aws = self._forms(self._accept(pb.info, count=False), ws, aws, cfg,
+                                           st.buf.data_ptr() + off[:-1], np.diff(off), count=False, skip=pb.futures)
+            pb.info, ws, aws, _ = self._orient(pb.info, ws, aws, cfg,
                                                st.buf.data_ptr() + off[:-1], np.diff(off), count=False, skip=pb.futures)
             nbytes = int(off[-1])
         else:

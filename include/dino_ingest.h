@@ -55,7 +55,9 @@
  *    dino_ctx_set_draft (JPEGs decoded at Pillow's Image.draft size, off by default) and
  *    dino_kernel_times ids 24 to 26; dino_ctx_set_exif_transpose (JPEGs leave the decode as
  *    ImageOps.exif_transpose gives them, off by default), dino_probe_orient, dino_orient_map,
- *    dino_orient_tile and dino_kernel_times ids 27 and 28.
+ *    dino_orient_tile and dino_kernel_times ids 27 and 28; dino_ctx_set_png_forms (PNG bit
+ *    depths 1, 2, 4 and 16 and Adam7 decoded on the device, off by default),
+ *    dino_probe_png_forms and dino_debug_png_forms_decode.
  */
 #ifndef DINO_INGEST_H
 #define DINO_INGEST_H
@@ -381,6 +383,33 @@ int dino_ctx_set_four_component(dino_ctx* ctx, int32_t on);
  * the Adler-32) is not examined.  dino_kernel_times id 23 ("k_png") sums the four PNG
  * kernels; dino_debug_region 10 is the joined zlib stream, 11 the inflated, still-filtered rows. */
 int dino_ctx_set_png(dino_ctx* ctx, int32_t on);
+
+/* The other PNG forms on a ctx with dino_ctx_set_png on, from the next call on: 0 (default) leaves
+ * them DINO_IMG_UNSUPPORTED; non-zero also decodes bit depths 1, 2, 4 and 16 and Adam7-interlaced
+ * files of every valid (colour type, depth) pair, bit for bit as Pillow 12's
+ * Image.open(..).convert("RGB"): samples below 8 bits unpacked MSB first (gray scaled by 255, 85
+ * or 17, palette looked up), the high byte of 16-bit RGB, RGBA and gray + alpha samples, and
+ * min(v, 255) of a 16-bit gray sample (what Pillow's I;16 -> RGB conversion gives).  The chunk
+ * rules are dino_ctx_set_png's.  DINO_EINVAL unless dino_ctx_set_png is on; turning that off
+ * suspends this option.  The kernels are timed under dino_kernel_times id 23 ("k_png"). */
+int dino_ctx_set_png_forms(dino_ctx* ctx, int32_t on);
+
+/* Which files such a ctx decodes beyond dino_ctx_set_png's (no GPU involved; the probes have no
+ * ctx and keep reporting kind 5 for them): form[i] = 1 and ws_need[i] = the decode-workspace
+ * bytes of image i where a ctx with both options on decodes it, 0 and 0 otherwise (a plain PNG,
+ * a PNG it still declines or on whose header Pillow raises, any other file).  The caller adds
+ * ws_need and the views' scratch (dino_augment_need) to the probe's numbers before dino_reserve.
+ * ptrs: absolute host addresses. */
+int dino_probe_png_forms(const uint64_t* ptrs, const int64_t* lens, int32_t batch, int32_t max_image_dim,
+                         uint8_t* form, int64_t* ws_need);
+
+/* Debug: the host model of that decode (the headers the kernels share, inflate with one lane).
+ * info = {status, width, height, form}: form 0 (nothing decoded) unless dino_probe_png_forms
+ * says 1 or the chunk walk fails the file; rgb receives 3 w h bytes when status is 0 (rgb_cap too
+ * small: DINO_IMG_NO_SPACE).  layout = {chunk bytes, stream region, carry row, inflated region,
+ * palette, RGB region, inflated bytes, rows of all passes}. */
+int dino_debug_png_forms_decode(const uint8_t* bytes, int64_t len, int32_t max_image_dim, uint8_t* rgb,
+                                int64_t rgb_cap, int32_t* info, int64_t* layout);
 
 /* Reduced-size JPEG decode on this ctx, from the next call on: n = 0 (default) decodes every
  * image at its coded size; n > 0 decodes each JPEG of one or three components as
