@@ -123,7 +123,8 @@ class MI355XBackend:
                  hbm_fraction: float = 0.15, host_workers: int | None = None, multiscan_route: str = "side",
                  side_ahead: int | None = None, resample_filter: str | None = None,
                  four_component: str = "host", png: str = "off", jpeg_draft: int = 0,
-                 exif_transpose: bool = False, png_forms: str = "plain") -> None:
+                 exif_transpose: bool = False, png_forms: str = "plain",
+                 webp: str = "off") -> None:
         # Pillow filter of every resize: None = bicubic everywhere (CPUBackend parity, which
         # ignores EvalAugSpec.interpolation too); a filter's name applies to every recipe;
         # "spec" honours EvalAugSpec.interpolation as the reference's GPU peer does
@@ -153,6 +154,13 @@ class MI355XBackend:
         from .fallback import check_png_forms
         check_png_forms(png_forms, png)
         self._png_forms = png_forms
+        # WebP files: "off" (default) leaves them zero-filled with status -1, as any non-JPEG;
+        # "host" hands every WebP to Pillow; "device" decodes the lossless ones (VP8L) in the
+        # kernels (k_vp8l, k_vp8l_inv) and hands the rest (lossy, animated, with EXIF) to Pillow.
+        # The UserAugSpec pipeline hands every WebP over under both
+        from .fallback import check_webp
+        check_webp(webp)
+        self._webp = webp
         # reduced-size JPEG decode, off at 0: N > 0 decodes every JPEG as Pillow does after
         # im.draft("RGB", (N, N)) (1/2, 1/4 or 1/8 of the coded size where both sides stay >= N;
         # fallback.draft_scale), on the device (libjpeg's reduced inverse DCTs) and in every
@@ -276,7 +284,7 @@ class MI355XBackend:
             return MI355XUserAugPipeline(source, aug_spec, getattr(source, "_batch_size", 1),
                                          out_dtype=pipeline_cfg.output_dtype, device=pipeline_cfg.device_id,
                                          max_image_dim=self._max_image_dim, workspace_bytes=self._workspace_bytes,
-                                         norm=norm, resample_filter=self.spec_filter(aug_spec), png=self._png,
+                                         norm=norm, resample_filter=self.spec_filter(aug_spec), png=self._png, webp=self._webp,
                                          jpeg_draft=self._jpeg_draft, exif_transpose=self._exif_transpose)
         if _is_dinov2_spec(aug_spec):
             aug_cfg = aug_spec.aug_cfg
@@ -325,6 +333,7 @@ class MI355XBackend:
             jpeg_draft=self._jpeg_draft,
             exif_transpose=self._exif_transpose,
             png_forms=self._png_forms,
+            webp=self._webp,
         )
 
     def build_pipeline_iterator(self, pipeline: Any, aug_spec: Any, output_map: list[str],

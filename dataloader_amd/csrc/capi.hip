@@ -68,6 +68,7 @@ struct dino_ctx {
   int32_t four_component = 0; // dino_ctx_set_four_component: read at each decode launch
   int32_t png = 0;            // dino_ctx_set_png: read at each decode launch
   int32_t png_forms = 0;      // dino_ctx_set_png_forms: read at each decode launch
+  int32_t webp = 0;           // dino_ctx_set_webp: read at each decode launch
   int32_t draft = 0;          // dino_ctx_set_draft: read at each decode launch
   int32_t exif_transpose = 0; // dino_ctx_set_exif_transpose: read at each decode launch
   OCtl* d_octl = nullptr;     // k_orient's tiles (allocated by the first dino_ctx_set_exif_transpose(ctx, 1))
@@ -156,7 +157,7 @@ int dino_decode_spans(dino_ctx* c, const uint8_t* d_bytes, const int64_t* d_offs
     return fail(DINO_EINVAL, "dino_decode: batch %s%lld exceeds ctx max_batch", "", batch);
   hipStream_t s = (hipStream_t)stream;
   DecodeArgs a{d_bytes, d_offsets, d_lengths, d_raw_mask, batch, c->lim.max_image_dim, c->d_desc, c->d_ws,
-               c->ws_size, c->geom, c->d_pctl, c->four_component, c->png, c->png && c->png_forms, c->draft,
+               c->ws_size, c->geom, c->d_pctl, c->four_component, c->png, c->png && c->png_forms, c->webp, c->draft,
                c->exif_transpose ? c->d_octl : nullptr};
   hipError_t e = launch_decode(a, s, c->tm());
   if (e != hipSuccess) return hip_fail(e, "dino_decode");
@@ -688,6 +689,100 @@ int dino_debug_png_forms_decode(const uint8_t* p, int64_t len, int32_t max_image
   memset(pal, 0, sizeof(pal));
   if (w.plte_off) memcpy(pal, p + w.plte_off, w.plte_n);
   if (!png_forms_unfilter_rows(inf.data(), f, pal, rgb)) info[0] = DINO_IMG_CORRUPT;
+  return DINO_OK;
+}
+
+int dino_ctx_set_webp(dino_ctx* c, int32_t on) {
+  if (!c) return fail(DINO_EINVAL, "dino_ctx_set_webp: null ctx%s%lld");
+  c->webp = on != 0;  // read at each launch (launch_decode)
+  return DINO_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// vp8l.hpp with one lane.
+struct HostVp8lIO {
+  int lane = 0, nl = 1;
+  const uint8_t* z;
+  int64_t zn;
+  uint32_t *cache, *stamp;
+  uint8_t* lens;
+  Vp8lGroup* stage;
+  void sync() {}
+  uint32_t in(int64_t i) const { return i >= 0 && i < zn ? z[i] : 0u; }
+  uint64_t ballot(bool b) const { return b ? 1u : 0u; }
+  int below(uint64_t) const { return 0; }
+  void amax(uint32_t* p, uint32_t v) const { *p = v > *p ? v : *p; }
+};
+
+// The host model of k_webphead, k_vp8l and k_vp8l_inv.  Returns the form dino_probe_webp states:
+// 0 not a WebP, 1 a WebP Pillow decides, 2 one the device decodes (d: its descriptor, status OK).
+// With rgb == nullptr it stops after the prologue, which is what decides between 1 and 2;
+// otherwise *st becomes the decode's status and rgb the pixels, feat the stream's features.
+int webp_host(const uint8_t* p, int64_t len, int32_t max_image_dim, ImgDesc* d, uint8_t* rgb, int* st, int32_t* feat) {
+  if (max_image_dim <= 0 || max_image_dim > kMaxImageDim) max_image_dim = kMaxImageDim;
+  d->kind = 0;
+  d->width = d->height = 0;
+  d->coef_bytes = 0;
+  d->status = DINO_IMG_CORRUPT;
+  if (!webp_signature(p, len)) return 0;
+  if (parse_webp_head(p, len, max_image_dim, d) != DINO_IMG_OK) return 1;
+  const int gcap = vp8l_groups_cap(*d);
+  const int64_t nsub = vp8l_sub_words(d->width, d->height), npx = (int64_t)d->width * d->height;
+  std::vector<Vp8lGroup> groups((size_t)(rgb ? gcap : 1) + 1);
+  std::vector<uint32_t> sub((size_t)nsub), lds(2 * kVp8lCacheMax), img((size_t)(rgb ? 2 * npx : 0) + 1);
+  std::vector<uint8_t> lens(kVp8lLens);
+  HostVp8lIO io;
+  io.z = p + d->scan_off, io.zn = d->scan_len, io.cache = lds.data(), io.stamp = lds.data() + kVp8lCacheMax;
+  io.lens = lens.data(), io.stage = &groups.back();
+  Vp8lPlan plan;
+  Vp8l<HostVp8lIO> dec(io, d->scan_len, groups.data(), rgb ? gcap : 1, sub.data(), nsub, plan);
+  if (!dec.prologue() || dec.W != d->width || dec.H != d->height || dec.ngroups > gcap) return 1;
+  if (!rgb) return 2;
+  *st = dec.body(img.data()) ? DINO_IMG_OK : DINO_IMG_CORRUPT;
+  for (int k = 0; k < 6; ++k) feat[k] = dec.plan.feat[k];
+  if (*st == DINO_IMG_OK) vp8l_inverse_host(dec.plan, sub.data(), img.data(), img.data() + npx, d->width, d->height, rgb);
+  return 2;
+}
+}  // namespace
+
+extern "C" {
+
+int dino_probe_webp(const uint64_t* ptrs, const int64_t* lens, int32_t batch, int32_t max_image_dim, uint8_t* form,
+                    int32_t* wh, int64_t* ws_need) {
+  if (batch < 0 || (batch > 0 && (!ptrs || !lens || !form || !wh || !ws_need)))
+    return fail(DINO_EINVAL, "dino_probe_webp: bad arguments%s%lld");
+  for (int32_t i = 0; i < batch; ++i) {
+    ImgDesc d;
+    form[i] = 0;
+    wh[2 * i] = wh[2 * i + 1] = 0;
+    ws_need[i] = 0;
+    if (lens[i] <= 0) continue;
+    form[i] = (uint8_t)webp_host((const uint8_t*)(uintptr_t)ptrs[i], lens[i], max_image_dim, &d, nullptr, nullptr, nullptr);
+    if (form[i] != 2) continue;
+    wh[2 * i] = d.width, wh[2 * i + 1] = d.height;
+    ws_need[i] = image_chunk_bytes(d).total();
+  }
+  return DINO_OK;
+}
+
+int dino_debug_webp_decode(const uint8_t* p, int64_t len, int32_t max_image_dim, uint8_t* rgb, int64_t rgb_cap,
+                           int32_t* info, int64_t* layout) {
+  if (!p || len <= 0 || !info || !layout || !rgb) return fail(DINO_EINVAL, "dino_debug_webp_decode: bad arguments%s%lld");
+  ImgDesc d;
+  for (int k = 0; k < 10; ++k) info[k] = 0;
+  for (int k = 0; k < 6; ++k) layout[k] = 0;
+  info[0] = DINO_IMG_CORRUPT;
+  if (webp_host(p, len, max_image_dim, &d, nullptr, nullptr, nullptr) != 2) return DINO_OK;
+  info[1] = d.width, info[2] = d.height, info[3] = 2;
+  const ChunkSizes z = image_chunk_bytes(d);
+  layout[0] = z.total(), layout[1] = z.coef, layout[2] = z.binfo, layout[3] = z.plane, layout[4] = z.rgb;
+  layout[5] = vp8l_groups_cap(d);
+  if ((int64_t)d.width * d.height * 3 > rgb_cap) return (info[0] = DINO_IMG_NO_SPACE, DINO_OK);
+  int st = DINO_IMG_CORRUPT;
+  webp_host(p, len, max_image_dim, &d, rgb, &st, info + 4);
+  info[0] = st;
   return DINO_OK;
 }
 

@@ -29,6 +29,7 @@
 //   kernels_timer.inc               host: KernelTimer, DINO_SYNC_CHECK
 //   kernels_png.inc                 k_pnghead, k_pngwalk, k_inflate, k_unfilter (opt-in)
 //   kernels_png_forms.inc           k_pnghead_forms, k_unfilter_forms: depths 1 / 2 / 4 / 16 and Adam7 (opt-in)
+//   kernels_webp.inc                k_webphead, k_vp8l, k_vp8l_inv: lossless WebP (opt-in)
 //   kernels_draft.inc               k_draft, k_idct_red, k_color_red: reduced-size JPEG decode (opt-in)
 //   kernels_orient.inc              k_exif, k_orient_scan, k_orient, k_orient_done: EXIF orientation applied (opt-in)
 //   kernels_launch.inc              host: init_launch_geom and every launch_*; k_pixel_ops
@@ -49,6 +50,8 @@
 #include "pscan.hpp"
 #include "png_parse.hpp"
 #include "png_forms.hpp"
+#include "webp_parse.hpp"
+#include "vp8l.hpp"
 #include "inflate.hpp"
 #include "sampler.hpp"
 
@@ -2393,7 +2396,7 @@ __device__ __forceinline__ void idct_image(const ImgDesc* __restrict__ desc, uin
   __shared__ uint8_t s_nat[80];
   const ImgDesc& d = desc[bk.y];
   if (d.status != DINO_IMG_OK || d.kind == 2 || (d.ncomp > kMaxComp) != (kComps > kMaxComp)) return;
-  if (kComps > kMaxComp && d.kind == kPngKind) return;  // (a PNG's ncomp is 4 too: k_idct4 only)
+  if (kComps > kMaxComp && d.kind >= kPngKind) return;  // (a PNG's or a WebP's ncomp is 4 too: k_idct4 only)
   if (d.draft_shift != 0) return;  // decoded at reduced size: k_idct_red
   // kind 1 (progressive / multi-scan): dense int16 coefficients in natural order,
   // component planes of bw x bh blocks (k_prog); kind 0: sparse entries + block records
@@ -2557,7 +2560,7 @@ constexpr int kColorBatch = DINO_COLOR_BATCH;  // quads whose loads a lane issue
 __global__ void __launch_bounds__(256) k_color4(const ImgDesc* __restrict__ desc, uint8_t* __restrict__ ws) {
   const BlkIdx bk = xcd_blk();
   const ImgDesc& d = desc[bk.y];
-  if (d.status != DINO_IMG_OK || d.ncomp != 4 || d.kind == kPngKind) return;
+  if (d.status != DINO_IMG_OK || d.ncomp != 4 || d.kind >= kPngKind) return;
   const PlaneView p0 = make_plane_view(d, ws, 0), p1 = make_plane_view(d, ws, 1);
   const PlaneView p2 = make_plane_view(d, ws, 2), p3 = make_plane_view(d, ws, 3);
   const bool ycck = d.color == kYCCK;
@@ -3518,6 +3521,7 @@ __global__ void __launch_bounds__(kVFinalThreads) k_vfinal(const ImgDesc* __rest
 #include "kernels_timer.inc"
 #include "kernels_png.inc"
 #include "kernels_png_forms.inc"
+#include "kernels_webp.inc"
 #include "kernels_draft.inc"
 #include "kernels_orient.inc"
 #include "kernels_launch.inc"

@@ -105,6 +105,8 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
   if (a.png) TIMED(tm, kKPng, s, (k_pnghead<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.max_dim, a.desc)));
   // a context with dino_ctx_set_png_forms on: the files k_pnghead declined for depth or interlace alone get theirs
   if (a.png && a.png_forms) TIMED(tm, kKPng, s, (k_pnghead_forms<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.desc)));
+  // a context with dino_ctx_set_webp on: WebP files get their descriptor before the plan
+  if (a.webp) TIMED(tm, kKPng, s, (k_webphead<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.max_dim, a.desc)));
   // a context with dino_ctx_set_draft on: the JPEGs that scale get their reduced size before the plan
   if (a.draft > 0) TIMED(tm, kKDraft, s, (k_draft<<<(B + 63) / 64, 64, 0, s>>>(a.desc, B, a.draft)));
   // a context with dino_ctx_set_exif_transpose on: every image gets its orientation before the plan
@@ -112,11 +114,12 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
     TIMED(tm, kKExif, s, (k_exif<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.desc)));
     TIMED(tm, kKExif, s, (k_orient_scan<<<1, 1024, 0, s>>>(a.desc, B, a.octl)));
   }
-  // (k_plan<true> also sizes kind-4 images; without the option there is none and k_plan<false> is the code it was;
-  // k_plan<.., true> gives the images that turn their second RGB region)
-  if (a.octl && a.png) TIMED(tm, kKPlan, s, (k_plan<true, true><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
+  // (k_plan<true> also sizes kind-4 and kind-6 images; without the options there is none and k_plan<false> is the
+  // code it was; k_plan<.., true> gives the images that turn their second RGB region)
+  const bool sized = a.png || a.webp;
+  if (a.octl && sized) TIMED(tm, kKPlan, s, (k_plan<true, true><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
   else if (a.octl) TIMED(tm, kKPlan, s, (k_plan<false, true><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
-  else if (a.png) TIMED(tm, kKPlan, s, (k_plan<true><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
+  else if (sized) TIMED(tm, kKPlan, s, (k_plan<true><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
   else TIMED(tm, kKPlan, s, (k_plan<false><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
   const int grid_ds = a.geom.grid_ds, grid1 = a.geom.grid1, grid3 = a.geom.grid3;
   TIMED(tm, kKDestuff, s, (k_destuff_count<<<grid_ds, kDestuffThreads, 0, s>>>(a.bytes, a.offsets, B, a.desc, a.ws)));
@@ -149,6 +152,10 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
     TIMED(tm, kKPng, s, (k_inflate<<<min(B, a.geom.grid_inf), 64, 0, s>>>(a.desc, a.ws, a.pctl, B)));
     TIMED(tm, kKPng, s, (k_unfilter<<<B, 64, 0, s>>>(a.desc, a.ws)));
     if (a.png_forms) TIMED(tm, kKPng, s, (k_unfilter_forms<<<B, 64, 0, s>>>(a.desc, a.ws)));
+  }
+  if (a.webp) {  // lossless WebP images (kind 6): no other context has one
+    TIMED(tm, kKPng, s, (k_vp8l<<<B, 64, 0, s>>>(a.bytes, a.offsets, a.desc, a.ws)));
+    TIMED(tm, kKPng, s, (k_vp8l_inv<<<B, kVp8lInvThreads, 0, s>>>(a.desc, a.ws)));
   }
   if (a.octl) {  // after every colour stage: the images k_exif tagged turn, then show their upright side
     TIMED(tm, kKOrient, s, (k_orient<<<a.geom.grid_or, 256, 0, s>>>(a.desc, a.ws, a.octl, B)));

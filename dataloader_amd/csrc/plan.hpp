@@ -7,6 +7,8 @@
 #include "progressive.hpp"
 #include "png_parse.hpp"
 #include "png_forms.hpp"
+#include "webp_parse.hpp"
+#include "vp8l.hpp"
 #include "pscan.hpp"
 #include "lscan.hpp"
 #include "resize.hpp"
@@ -90,7 +92,17 @@ DHD DsRole ds_part_role(int part, int lead, int n, int E, int ds_items) {
 DHD int64_t rgb_region_bytes(int64_t w, int64_t h) { return align16(w * h * 3 + 16); }
 DHD int64_t orient_extra_bytes(int64_t w, int64_t h) { return align256(rgb_region_bytes(w, h)); }
 
-// kPng: the caller may hold PNG images (kind 4).  k_plan of a context without dino_ctx_set_png is
+// Groups a lossless WebP (kind 6) may name: its table area holds that many Vp8lGroup records, the
+// whole entropy image at most (a group a block of 4 x 4 pixels).  A file with more is declined by
+// dino_probe_webp (Pillow decodes it), so that one image reserves at most 256 x 6432 bytes = 1.6 MB
+// of tables; libwebp's encoder merges its histograms down to a few dozen.
+constexpr int kVp8lMaxGroups = 256;
+DHD int vp8l_groups_cap(const ImgDesc& d) {
+  const int64_t px = vp8l_block_px(d.width, d.height);
+  return px < kVp8lMaxGroups ? (int)px : kVp8lMaxGroups;
+}
+
+// kPng: the caller may hold PNG images (kind 4) or lossless WebP images (kind 6).  k_plan of a context without dino_ctx_set_png is
 // instantiated without them and stays the code it was.  kOrient: the caller's k_exif wrote every
 // image's orientation (dino_ctx_set_exif_transpose); without it pad0 is not read and the layout
 // is the one it was.
@@ -107,6 +119,12 @@ DHD ChunkSizes image_chunk_bytes(const ImgDesc& d) {
     if (png_is_form(d)) z.coef = align16(8 * png_form_max_units(d) + 16);  // (k_unfilter_forms: 8 bytes a unit)
     z.plane = align16(png_inflated_bytes(d) + 64);
     z.htab = kPngPalBytes;
+    return chunk_finish(z);
+  }
+  if (kPng && d.kind == kWebpKind) {  // Vp8lPlan + the sub-images, the groups' codes, the ARGB plane (the payload is read in place)
+    z.coef = align16((int64_t)sizeof(Vp8lPlan) + 4 * vp8l_sub_words(d.width, d.height));
+    z.binfo = (int64_t)vp8l_groups_cap(d) * (int64_t)sizeof(Vp8lGroup);
+    z.plane = align16((int64_t)d.width * d.height * 4 + 64);
     return chunk_finish(z);
   }
   // the planes hold a byte per coefficient of the dense int16 layout coef_bytes counts

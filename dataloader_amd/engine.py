@@ -89,6 +89,7 @@ class IngestEngine:
         self.four_component = False  # set_four_component's choice (False: CMYK / YCCK files report status 1)
         self.png = False  # set_png's choice (False: PNG files report status -1, as any non-JPEG)
         self.png_forms = False  # set_png_forms's choice (False: depths 1 / 2 / 4 / 16 and Adam7 report status 1)
+        self.webp = False  # set_webp's choice (False: WebP files report status -1, as any non-JPEG)
         self.draft = 0  # set_draft's choice (0: every JPEG decodes at its coded size)
         self.exif_transpose = False  # set_exif_transpose's choice (False: the Orientation tag is ignored)
 
@@ -186,6 +187,14 @@ class IngestEngine:
         ``fallback.probe_png_forms`` names them and their workspace bytes."""
         _lib.check(self.lib.dino_ctx_set_png_forms(self._ctx, int(bool(on))), "dino_ctx_set_png_forms")
         self.png_forms = bool(on)
+
+    def set_webp(self, on: bool) -> None:
+        """Decode lossless WebP files (VP8L, alone or in a VP8X container without animation or
+        EXIF) on this context (``True``) or report every WebP ``DINO_IMG_CORRUPT`` (``False``, the
+        default) from the next call on (``dino_ctx_set_webp``).  The probes keep reporting these
+        files as status -1: ``fallback.probe_webp`` names them and their workspace bytes."""
+        _lib.check(self.lib.dino_ctx_set_webp(self._ctx, int(bool(on))), "dino_ctx_set_webp")
+        self.webp = bool(on)
 
     def set_draft(self, n: int) -> None:
         """Decode this context's JPEGs of one or three components at the size of Pillow's

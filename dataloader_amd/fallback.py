@@ -124,6 +124,57 @@ def accept_png_forms(info: np.ndarray, form: np.ndarray, ws: np.ndarray, cfg=Non
     return out, int(np.asarray(ws, np.int64)[m].sum()), aws
 
 
+WEBP_MODES = ("off", "host", "device")
+WEBP_NONE, WEBP_DECLINED, WEBP_DEVICE = 0, 1, 2  # dino_probe_webp's forms
+
+
+def check_webp(mode: str) -> None:
+    if mode not in WEBP_MODES:
+        raise ValueError(f"webp must be 'off', 'host' or 'device', not {mode!r}")
+
+
+def probe_webp(ptrs: np.ndarray, lens: np.ndarray, max_image_dim: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """``dino_probe_webp`` over images where they lie (absolute host addresses + lengths) ->
+    (form int32[B, 3], ws int64[B]).  ``form[:, 0]`` is 0 for a file that is no WebP, 1 for a
+    WebP a context with ``dino_ctx_set_webp`` on does not decode (lossy, animated, with EXIF,
+    unverified: Pillow decides it) and 2 for a lossless WebP it decodes, with the image's width
+    and height in columns 1 and 2 and its decode-workspace bytes in ``ws``."""
+    p = np.ascontiguousarray(ptrs, np.uint64)
+    n = np.ascontiguousarray(lens, np.int64)
+    flag = np.zeros(len(p), np.uint8)
+    wh = np.zeros((len(p), 2), np.int32)
+    ws = np.zeros(len(p), np.int64)
+    _lib.check(_lib.load().dino_probe_webp(p.ctypes.data_as(ctypes.c_void_p), n.ctypes.data_as(ctypes.c_void_p), len(p),
+                                           int(max_image_dim), flag.ctypes.data_as(ctypes.c_void_p),
+                                           wh.ctypes.data_as(ctypes.c_void_p), ws.ctypes.data_as(ctypes.c_void_p)),
+               "dino_probe_webp")
+    return np.concatenate([flag[:, None].astype(np.int32), wh], 1), ws
+
+
+def accept_webp(info: np.ndarray, form: np.ndarray, ws: np.ndarray, webp: str = "device",
+                cfg=None) -> tuple[np.ndarray, int, int]:
+    """The probe's info (status -1, kind -1 for every WebP) as a pipeline with the option ``webp``
+    treats the batch.  ``"device"``: rows with ``form[:, 0] == 2`` become status 0, kind 1 with
+    their width and height (decoded on contexts with ``dino_ctx_set_webp`` on and routed like any
+    coefficient-buffer image), rows with form 1 status ``IMG_UNSUPPORTED`` (handed to Pillow).
+    ``"host"``: both become ``IMG_UNSUPPORTED``.  ``"off"``: nothing changes.  Returns (a copy of
+    info, decode-workspace bytes to add, augment-workspace bytes to add): the probe counted
+    neither; the last is ``augment_need`` of the device's rows for ``cfg`` (0 without)."""
+    check_webp(webp)
+    out = np.array(info, np.int32, copy=True)
+    if webp == "off":
+        return out, 0, 0
+    form = np.asarray(form)
+    mine = (out[:, 0] == IMG_CORRUPT) & (out[:, 3] == -1)
+    dev = mine & (form[:, 0] == WEBP_DEVICE) & (webp == "device")
+    out[mine & (form[:, 0] != WEBP_NONE) & ~dev, 0] = IMG_UNSUPPORTED
+    out[dev, 0] = 0
+    out[dev, 1:3] = form[dev, 1:3]
+    out[dev, 3] = KIND_MULTISCAN
+    aws = augment_need(out[dev], cfg) if cfg is not None and dev.any() else 0
+    return out, int(np.asarray(ws, np.int64)[dev].sum()), aws
+
+
 def four_component_mask(info: np.ndarray) -> np.ndarray:
     """Rows of a probed batch that are four-component (CMYK / YCCK) files a context with
     ``dino_ctx_set_four_component`` on decodes (status 1, kind 3)."""

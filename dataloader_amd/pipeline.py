@@ -129,7 +129,7 @@ class MI355XAugPipeline:
                  multiscan_host_max: int | None = None, prefetch: int | None = None,
                  start_host_pool: bool = False, side_ahead: int = 64, resample_filter=None,
                  four_component: str = "host", png: str = "off", jpeg_draft: int = 0,
-                 exif_transpose: bool = False, png_forms: str = "plain"):
+                 exif_transpose: bool = False, png_forms: str = "plain", webp: str = "off"):
         self._source = source
         # EXIF orientation applied (ImageOps.exif_transpose before convert("RGB")): every slot and
         # side context gets dino_ctx_set_exif_transpose and turns the JPEGs whose tag its walk
@@ -153,6 +153,12 @@ class MI355XAugPipeline:
         # the probes keep reporting those files as declined, fallback.accept_png_forms takes them back (_forms)
         fallback.check_png_forms(png_forms, png)
         self._png_forms = png_forms == "all"
+        # WebP files: "off" leaves them zero-filled (status -1, as any non-JPEG), "host" hands every one
+        # to Pillow, "device" decodes the lossless ones on the GPU (every slot and side context gets
+        # dino_ctx_set_webp) and hands the rest to Pillow; the probes report a WebP as any non-JPEG,
+        # fallback.accept_webp rewrites the rows (_forms)
+        fallback.check_webp(webp)
+        self._webp = webp
         self._aug_cfg = aug_cfg
         # four-component (CMYK / YCCK) JPEGs: "host" hands them to Pillow, "device" decodes them in
         # the kernels (every slot and side context gets dino_ctx_set_four_component) and routes them
@@ -192,7 +198,8 @@ class MI355XAugPipeline:
         # GPU decoder left to Pillow, and workspace regrowths
         # four_component: CMYK / YCCK images kept on the device (four_component="device")
         self.stats = {"batches": 0, "images": 0, "status": Counter(), "host_decoded": 0, "reserves": 0,
-                      "side_decoded": 0, "four_component": 0, "png_device": 0, "png_host": 0}
+                      "side_decoded": 0, "four_component": 0, "png_device": 0, "png_host": 0,
+                      "webp_device": 0, "webp_host": 0}
         if self._exif:  # images the contexts turned / images handed to Pillow because the walk verified nothing
             self.stats.update(orient_device=0, orient_host=0)
         # host-side seconds per phase: pull / pack / probe (host half), wait (launch thread
@@ -257,6 +264,8 @@ class MI355XAugPipeline:
                 eng.set_png(True)
             if self._png_forms:
                 eng.set_png_forms(True)
+            if self._webp == "device":
+                eng.set_webp(True)
             if self._draft:
                 eng.set_draft(self._draft)
             if self._exif:
@@ -450,7 +459,19 @@ class MI355XAugPipeline:
         decode the batch (``fallback.accept_png_forms``: the declined PNGs of the extended forms
         become coefficient-buffer images, their workspace and view scratch added), moved from
         ``png_host`` to ``png_device`` in ``stats`` once per batch.  ``skip``: images already
-        handed over.  Returns (info, ws, aws)."""
+        handed over.  Returns (info, ws, aws).  With ``webp`` on, the WebP rows come first
+        (``fallback.accept_webp``: the lossless files become coefficient-buffer images with their
+        workspace and view scratch, the others go to Pillow), counted as ``webp_device`` / ``webp_host``."""
+        if self._webp != "off" and ((info[:, 0] == fallback.IMG_CORRUPT) & (info[:, 3] == -1)).any():
+            form, need = fallback.probe_webp(ptrs, lens, self._max_image_dim)
+            for i in skip:
+                form[int(i), 0] = 0
+            info, extra, extra_aws = fallback.accept_webp(info, form, need, self._webp, cfg)
+            ws, aws = ws + extra, aws + extra_aws
+            if count:
+                dev = int(((form[:, 0] == fallback.WEBP_DEVICE) & (info[:, 0] == 0)).sum())
+                self.stats["webp_device"] += dev
+                self.stats["webp_host"] += int((form[:, 0] != fallback.WEBP_NONE).sum()) - dev
         if not self._png_forms or not (info[:, 3] == fallback.KIND_PNG_DECLINED).any():
             return info, ws, aws
         form, need = fallback.probe_png_forms(ptrs, lens, self._max_image_dim)
@@ -633,7 +654,8 @@ class MI355XAugPipeline:
                                                     stream_set=self._stream_set, lanes=lanes,
                                                     four_component=self._four_component == "device",
                                                     png=self._png == "device", draft=self._draft,
-                                                    exif_transpose=self._exif, png_forms=self._png_forms)
+                                                    exif_transpose=self._exif, png_forms=self._png_forms,
+                                                    webp=self._webp == "device")
             self.stats["side_lanes"] = lanes
         if pb.jpegs is not None:
             imgs = {int(i): pb.jpegs[i] for i in idx}

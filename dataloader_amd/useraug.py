@@ -34,7 +34,7 @@ class MI355XUserAugPipeline:
 
     def __init__(self, source: Any, spec, batch_size: int, out_dtype="bf16", device: int = 0,
                  max_image_dim: int = 0, workspace_bytes: int = 0, norm=None, resample_filter=None,
-                 png: str = "off", jpeg_draft: int = 0, exif_transpose: bool = False):
+                 png: str = "off", jpeg_draft: int = 0, exif_transpose: bool = False, webp: str = "off"):
         self._source = source
         # EXIF orientation applied: on the context, and by Pillow for the files it does not verify
         self._exif = bool(exif_transpose)
@@ -44,6 +44,9 @@ class MI355XUserAugPipeline:
         # decode over to it (this pipeline's context does not decode them), as four-component files are
         fallback.check_png(png)
         self._png = png
+        # WebP files: the same ("host" and "device" both hand every WebP over to Pillow)
+        fallback.check_webp(webp)
+        self._webp = webp
         self._spec = spec
         self._batch_size = int(batch_size)
         self._out = _out_code(out_dtype)
@@ -95,6 +98,10 @@ class MI355XUserAugPipeline:
         png = "off" if self._png == "off" else "host"
         orient = fallback.probe_orient_list(jpegs) if self._exif else np.zeros(len(jpegs), np.uint8)
         info, extra, _ = fallback.accept_orient(info, orient)  # (unverified tags: handed over below)
+        if self._webp != "off":  # every WebP becomes IMG_UNSUPPORTED: handed over below
+            o = offsets.numpy()
+            form, need = fallback.probe_webp(host_buf.data_ptr() + o[:-1], np.diff(o), self._max_image_dim)
+            info, _, _ = fallback.accept_webp(info, form, need, "host")
         if np.isin(info[:, 0], (fallback.IMG_UNSUPPORTED, fallback.IMG_LIMIT)).any() or \
                 (png != "off" and fallback.png_mask(info).any()):
             jpegs, n, rm = fallback.hand_over(list(jpegs), info[:, 0], kind=info[:, 3], png=png, draft=self._draft,

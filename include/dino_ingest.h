@@ -57,7 +57,8 @@
  *    ImageOps.exif_transpose gives them, off by default), dino_probe_orient, dino_orient_map,
  *    dino_orient_tile and dino_kernel_times ids 27 and 28; dino_ctx_set_png_forms (PNG bit
  *    depths 1, 2, 4 and 16 and Adam7 decoded on the device, off by default),
- *    dino_probe_png_forms and dino_debug_png_forms_decode.
+ *    dino_probe_png_forms and dino_debug_png_forms_decode; dino_ctx_set_webp (lossless WebP
+ *    decoded on the device, off by default), dino_probe_webp and dino_debug_webp_decode.
  */
 #ifndef DINO_INGEST_H
 #define DINO_INGEST_H
@@ -410,6 +411,37 @@ int dino_probe_png_forms(const uint64_t* ptrs, const int64_t* lens, int32_t batc
  * palette, RGB region, inflated bytes, rows of all passes}. */
 int dino_debug_png_forms_decode(const uint8_t* bytes, int64_t len, int32_t max_image_dim, uint8_t* rgb,
                                 int64_t rgb_cap, int32_t* info, int64_t* layout);
+
+/* Lossless WebP on this ctx, from the next call on: 0 (default) leaves every WebP file
+ * DINO_IMG_CORRUPT, as any non-JPEG; non-zero decodes the files whose container the device
+ * verifies, bit for bit as Pillow 12's Image.open(..).convert("RGB"): RIFF / WEBP holding one VP8L
+ * chunk, alone or in a VP8X container without animation beside ICCP, XMP or unknown chunks (alpha
+ * is dropped, as Pillow's RGBA -> RGB does).  Every other WebP (lossy VP8, ALPH, ANIM / ANMF, an
+ * EXIF chunk, sizes that do not add up, a side above max_image_dim) reports DINO_IMG_UNSUPPORTED:
+ * the caller hands it to Pillow.  An error inside the VP8L stream, on which Pillow raises, is
+ * DINO_IMG_CORRUPT.  The kernels are timed under dino_kernel_times id 23 ("k_png"). */
+int dino_ctx_set_webp(dino_ctx* ctx, int32_t on);
+
+/* Which files such a ctx decodes (no GPU involved; the probes have no ctx and keep reporting
+ * status -1, kind -1 for a WebP): form[i] = 0 not a WebP, 1 a WebP the ctx does not decode (Pillow
+ * decides it), 2 a WebP it decodes, with wh[2 i], wh[2 i + 1] = width, height and ws_need[i] = the
+ * decode-workspace bytes of image i (0 unless form is 2).  Form 2 needs the container walk, the
+ * VP8L header and the stream's prologue (the transforms' sub-images and the entropy image, decoded
+ * here on the host) to be sound and to name at most 256 groups of codes.  The caller adds ws_need
+ * and the views' scratch (dino_augment_need) to the probe's numbers before dino_reserve.
+ * ptrs: absolute host addresses. */
+int dino_probe_webp(const uint64_t* ptrs, const int64_t* lens, int32_t batch, int32_t max_image_dim, uint8_t* form,
+                    int32_t* wh, int64_t* ws_need);
+
+/* Debug: the host model of that decode (the text the kernels compile, run with one lane).
+ * info = {status, width, height, form, transforms seen (bit per type: 0 predictor, 1 cross-colour,
+ * 2 subtract-green, 3 colour indexing), colour-cache bits, groups, bundling bits + 1 (0: no colour
+ * indexing), a distance code <= 120 occurred, one above 120 occurred}; status is DINO_IMG_CORRUPT
+ * and the rest 0 unless dino_probe_webp says 2; rgb receives 3 w h bytes when status is 0 (rgb_cap
+ * too small: DINO_IMG_NO_SPACE).  layout = {chunk bytes, plan + sub-image region, code region,
+ * ARGB plane, RGB region, groups the code region holds}. */
+int dino_debug_webp_decode(const uint8_t* bytes, int64_t len, int32_t max_image_dim, uint8_t* rgb, int64_t rgb_cap,
+                           int32_t* info, int64_t* layout);
 
 /* Reduced-size JPEG decode on this ctx, from the next call on: n = 0 (default) decodes every
  * image at its coded size; n > 0 decodes each JPEG of one or three components as

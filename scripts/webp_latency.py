@@ -1,0 +1,51 @@
+"""Latency of one 640x480 image through the lossless-WebP kernels beside the same pixels as a PNG
+through the PNG kernels, on one build: the "k_png" timer slot (every kernel of the format, HIP
+events) per decode call.  python scripts/webp_latency.py [reps]"""
+
+import io
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+from PIL import Image
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from dataloader_amd import fallback  # noqa: E402
+from dataloader_amd.engine import IngestEngine, pack_jpegs  # noqa: E402
+from dataloader_amd.tario import spans_of  # noqa: E402
+
+
+def main():
+    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+    dev = torch.device("cuda", 0)
+    im = Image.open(Path(__file__).resolve().parents[1] / "tests" / "golden" / "prog_640x480.jpg").convert("RGB")
+    files = {}
+    for fmt, kw in (("WEBP", {"lossless": True, "method": 4}), ("PNG", {})):
+        f = io.BytesIO()
+        im.save(f, fmt, **kw)
+        files[fmt] = f.getvalue()
+    for fmt, data in files.items():
+        eng = IngestEngine(dev, max_batch=1, max_views=1, max_crop_size=8)
+        eng.set_webp(True) if fmt == "WEBP" else eng.set_png(True)
+        ptrs, lens, _keep = spans_of([data])
+        eng.reserve(int(fallback.probe_webp(ptrs, lens)[1].sum()) + (64 << 20), 0)
+        buf, off = pack_jpegs([data], pin=True)
+        d_bytes, d_off = buf.to(dev), off.to(dev)
+        eng.set_timing(True)
+        times = []
+        for r in range(reps + 3):
+            info = eng.decode(d_bytes, d_off, 1).cpu().numpy()
+            torch.cuda.synchronize()
+            t = eng.kernel_times()["k_png"][0]
+            if r >= 3:
+                times.append(t)
+        got = eng.copy_rgb(0, 640, 480).cpu().numpy()
+        assert info[0, 0] == 0 and np.array_equal(got, np.asarray(im)), fmt
+        eng.close()
+        print(f"{fmt}: {len(data)} bytes, k_png slot per decode: median {np.median(times):.3f} ms, "
+              f"min {min(times):.3f}, max {max(times):.3f} over {reps} decodes")
+
+
+if __name__ == "__main__":
+    main()
