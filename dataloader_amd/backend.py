@@ -124,7 +124,7 @@ class MI355XBackend:
                  side_ahead: int | None = None, resample_filter: str | None = None,
                  four_component: str = "host", png: str = "off", jpeg_draft: int = 0,
                  exif_transpose: bool = False, png_forms: str = "plain",
-                 webp: str = "off") -> None:
+                 webp: str = "off", webp_forms: str = "lossless") -> None:
         # Pillow filter of every resize: None = bicubic everywhere (CPUBackend parity, which
         # ignores EvalAugSpec.interpolation too); a filter's name applies to every recipe;
         # "spec" honours EvalAugSpec.interpolation as the reference's GPU peer does
@@ -161,6 +161,11 @@ class MI355XBackend:
         from .fallback import check_webp
         check_webp(webp)
         self._webp = webp
+        # "all" (needs webp="device"): the lossy ones (VP8 key frames) decode in the kernels too
+        # (k_vp8_tok, k_vp8_rec, k_vp8_rgb); "lossless" (default) keeps handing them to Pillow
+        from .fallback import check_webp_forms
+        check_webp_forms(webp_forms, webp)
+        self._webp_forms = webp_forms
         # reduced-size JPEG decode, off at 0: N > 0 decodes every JPEG as Pillow does after
         # im.draft("RGB", (N, N)) (1/2, 1/4 or 1/8 of the coded size where both sides stay >= N;
         # fallback.draft_scale), on the device (libjpeg's reduced inverse DCTs) and in every
@@ -334,6 +339,7 @@ class MI355XBackend:
             exif_transpose=self._exif_transpose,
             png_forms=self._png_forms,
             webp=self._webp,
+            webp_forms=self._webp_forms,
         )
 
     def build_pipeline_iterator(self, pipeline: Any, aug_spec: Any, output_map: list[str],

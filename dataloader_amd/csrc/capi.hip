@@ -69,6 +69,7 @@ struct dino_ctx {
   int32_t png = 0;            // dino_ctx_set_png: read at each decode launch
   int32_t png_forms = 0;      // dino_ctx_set_png_forms: read at each decode launch
   int32_t webp = 0;           // dino_ctx_set_webp: read at each decode launch
+  int32_t webp_forms = 0;     // dino_ctx_set_webp_forms: read at each decode launch
   int32_t draft = 0;          // dino_ctx_set_draft: read at each decode launch
   int32_t exif_transpose = 0; // dino_ctx_set_exif_transpose: read at each decode launch
   OCtl* d_octl = nullptr;     // k_orient's tiles (allocated by the first dino_ctx_set_exif_transpose(ctx, 1))
@@ -157,7 +158,8 @@ int dino_decode_spans(dino_ctx* c, const uint8_t* d_bytes, const int64_t* d_offs
     return fail(DINO_EINVAL, "dino_decode: batch %s%lld exceeds ctx max_batch", "", batch);
   hipStream_t s = (hipStream_t)stream;
   DecodeArgs a{d_bytes, d_offsets, d_lengths, d_raw_mask, batch, c->lim.max_image_dim, c->d_desc, c->d_ws,
-               c->ws_size, c->geom, c->d_pctl, c->four_component, c->png, c->png && c->png_forms, c->webp, c->draft,
+               c->ws_size, c->geom, c->d_pctl, c->four_component, c->png, c->png && c->png_forms, c->webp,
+               c->webp && c->webp_forms, c->draft,
                c->exif_transpose ? c->d_octl : nullptr};
   hipError_t e = launch_decode(a, s, c->tm());
   if (e != hipSuccess) return hip_fail(e, "dino_decode");
@@ -695,6 +697,118 @@ int dino_debug_png_forms_decode(const uint8_t* p, int64_t len, int32_t max_image
 int dino_ctx_set_webp(dino_ctx* c, int32_t on) {
   if (!c) return fail(DINO_EINVAL, "dino_ctx_set_webp: null ctx%s%lld");
   c->webp = on != 0;  // read at each launch (launch_decode)
+  return DINO_OK;
+}
+
+int dino_ctx_set_webp_forms(dino_ctx* c, int32_t on) {
+  if (!c) return fail(DINO_EINVAL, "dino_ctx_set_webp_forms: null ctx%s%lld");
+  if (on && !c->webp) return fail(DINO_EINVAL, "dino_ctx_set_webp_forms: needs dino_ctx_set_webp on%s%lld");
+  c->webp_forms = on != 0;  // read at each launch (launch_decode), where it holds only beside webp
+  return DINO_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// vp8.hpp with one lane.
+struct HostVp8IO {
+  int lane = 0, nl = 1;
+  const uint8_t* z;
+  int64_t zn;
+  void sync() {}
+  uint32_t in(int, int64_t i) const { return i >= 0 && i < zn ? z[i] : 0u; }
+};
+
+// The host model of k_vp8head, k_vp8_tok, k_vp8_rec and k_vp8_rgb.  Returns whether a context
+// with dino_ctx_set_webp_forms on decodes the file (d: its kind-7 descriptor): the container
+// walk, the frame tag and the bool-coded frame header decide.  With rgb != nullptr it goes on:
+// *st becomes the decode's status, rgb the pixels, cover the frame record's coverage.
+bool vp8_host(const uint8_t* p, int64_t len, int32_t max_image_dim, ImgDesc* d, uint8_t* rgb, int* st, int32_t* cover) {
+  if (max_image_dim <= 0 || max_image_dim > kMaxImageDim) max_image_dim = kMaxImageDim;
+  d->kind = 0;
+  d->width = d->height = 0;
+  d->coef_bytes = 0;
+  d->status = DINO_IMG_CORRUPT;
+  if (!webp_signature(p, len) || parse_vp8_head(p, len, max_image_dim, d) != DINO_IMG_OK) return false;
+  const int W = d->width, H = d->height, mbw = vp8_mbs(W), mbh = vp8_mbs(H);
+  const int64_t nmb = vp8_nmb(W, H);
+  HostVp8IO io;
+  io.z = p + d->scan_off, io.zn = d->scan_len;
+  Vp8Frame F;
+  Vp8Mb M;
+  std::vector<uint8_t> proba(1056);
+  std::vector<uint32_t> tmode((size_t)mbw);
+  std::vector<uint16_t> tnz((size_t)mbw);
+  std::vector<int16_t> cbuf(400);
+  Vp8Tok<HostVp8IO> tok(io, F, proba.data(), tmode.data(), tnz.data(), cbuf.data(), M);
+  const int hs = tok.header(d->scan_len, mbw);
+  if (hs == kWebpDecline) return false;
+  if (!rgb) return true;
+  *st = DINO_IMG_CORRUPT;
+  if (hs != DINO_IMG_OK) return true;
+  std::vector<int16_t> coef((size_t)(384 * nmb));
+  std::vector<Vp8Mb> mbs((size_t)nmb);
+  const bool ok = tok.body(coef.data(), mbs.data());
+  for (int k = 0; k < 8; ++k) cover[k] = F.cover[k];
+  if (!ok) return true;
+  std::vector<uint32_t> planes((size_t)(96 * nmb) + 16);  // (word-aligned: rows go back as words)
+  uint8_t* Y = (uint8_t*)planes.data();
+  uint8_t *U = Y + 256 * nmb, *V = U + 64 * nmb;
+  alignas(16) uint8_t T[kVp8TileBytes];
+  int16_t R[384];
+  for (int my = 0; my < mbh; ++my)
+    for (int mx = 0; mx < mbw; ++mx) {
+      const int64_t mb = (int64_t)my * mbw + mx;
+      vp8_rec_mb(io, mx, my, mbw, coef.data() + 384 * mb, mbs[(size_t)mb], Y, U, V, T, R);
+    }
+  if (F.filter_type)
+    for (int my = 0; my < mbh; ++my)
+      for (int mx = 0; mx < mbw; ++mx) vp8_filter_mb(io, mx, my, mbw, F, mbs[(size_t)((int64_t)my * mbw + mx)], Y, U, V);
+  for (int y = 0; y < H; ++y)
+    for (int x = 0; x < W; ++x) {
+      const uint32_t c = vp8_rgb_px(Y, U, V, mbw, x, y, W, H);
+      uint8_t* o = rgb + ((int64_t)y * W + x) * 3;
+      o[0] = (uint8_t)c, o[1] = (uint8_t)(c >> 8), o[2] = (uint8_t)(c >> 16);
+    }
+  *st = DINO_IMG_OK;
+  return true;
+}
+}  // namespace
+
+extern "C" {
+
+int dino_probe_webp_forms(const uint64_t* ptrs, const int64_t* lens, int32_t batch, int32_t max_image_dim, uint8_t* form,
+                          int32_t* wh, int64_t* ws_need) {
+  if (batch < 0 || (batch > 0 && (!ptrs || !lens || !form || !wh || !ws_need)))
+    return fail(DINO_EINVAL, "dino_probe_webp_forms: bad arguments%s%lld");
+  for (int32_t i = 0; i < batch; ++i) {
+    ImgDesc d;
+    form[i] = 0;
+    wh[2 * i] = wh[2 * i + 1] = 0;
+    ws_need[i] = 0;
+    if (lens[i] <= 0 || !vp8_host((const uint8_t*)(uintptr_t)ptrs[i], lens[i], max_image_dim, &d, nullptr, nullptr, nullptr)) continue;
+    form[i] = 1;
+    wh[2 * i] = d.width, wh[2 * i + 1] = d.height;
+    ws_need[i] = image_chunk_bytes(d).total();
+  }
+  return DINO_OK;
+}
+
+int dino_debug_vp8_decode(const uint8_t* p, int64_t len, int32_t max_image_dim, uint8_t* rgb, int64_t rgb_cap,
+                          int32_t* info, int64_t* layout) {
+  if (!p || len <= 0 || !info || !layout || !rgb) return fail(DINO_EINVAL, "dino_debug_vp8_decode: bad arguments%s%lld");
+  ImgDesc d;
+  for (int k = 0; k < 12; ++k) info[k] = 0;
+  for (int k = 0; k < 5; ++k) layout[k] = 0;
+  info[0] = DINO_IMG_CORRUPT;
+  if (!vp8_host(p, len, max_image_dim, &d, nullptr, nullptr, nullptr)) return DINO_OK;
+  info[1] = d.width, info[2] = d.height, info[3] = 1;
+  const ChunkSizes z = image_chunk_bytes(d);
+  layout[0] = z.total(), layout[1] = z.coef, layout[2] = z.binfo, layout[3] = z.plane, layout[4] = z.rgb;
+  if ((int64_t)d.width * d.height * 3 > rgb_cap) return (info[0] = DINO_IMG_NO_SPACE, DINO_OK);
+  int st = DINO_IMG_CORRUPT;
+  vp8_host(p, len, max_image_dim, &d, rgb, &st, info + 4);
+  info[0] = st;
   return DINO_OK;
 }
 

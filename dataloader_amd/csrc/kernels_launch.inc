@@ -107,6 +107,8 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
   if (a.png && a.png_forms) TIMED(tm, kKPng, s, (k_pnghead_forms<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.desc)));
   // a context with dino_ctx_set_webp on: WebP files get their descriptor before the plan
   if (a.webp) TIMED(tm, kKPng, s, (k_webphead<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.max_dim, a.desc)));
+  // a context with dino_ctx_set_webp_forms on: the lossy files k_webphead declined get theirs
+  if (a.webp && a.webp_forms) TIMED(tm, kKPng, s, (k_vp8head<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.max_dim, a.desc)));
   // a context with dino_ctx_set_draft on: the JPEGs that scale get their reduced size before the plan
   if (a.draft > 0) TIMED(tm, kKDraft, s, (k_draft<<<(B + 63) / 64, 64, 0, s>>>(a.desc, B, a.draft)));
   // a context with dino_ctx_set_exif_transpose on: every image gets its orientation before the plan
@@ -156,6 +158,11 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
   if (a.webp) {  // lossless WebP images (kind 6): no other context has one
     TIMED(tm, kKPng, s, (k_vp8l<<<B, 64, 0, s>>>(a.bytes, a.offsets, a.desc, a.ws)));
     TIMED(tm, kKPng, s, (k_vp8l_inv<<<B, kVp8lInvThreads, 0, s>>>(a.desc, a.ws)));
+  }
+  if (a.webp && a.webp_forms) {  // lossy WebP images (kind 7): no other context has one
+    TIMED(tm, kKPng, s, (k_vp8_tok<<<B, 64, 0, s>>>(a.bytes, a.offsets, a.desc, a.ws)));
+    TIMED(tm, kKPng, s, (k_vp8_rec<<<B, kVp8RecThreads, 0, s>>>(a.desc, a.ws)));
+    TIMED(tm, kKPng, s, (k_vp8_rgb<<<dim3(kVp8RgbWgs, B), 256, 0, s>>>(a.desc, a.ws)));
   }
   if (a.octl) {  // after every colour stage: the images k_exif tagged turn, then show their upright side
     TIMED(tm, kKOrient, s, (k_orient<<<a.geom.grid_or, 256, 0, s>>>(a.desc, a.ws, a.octl, B)));

@@ -9,6 +9,7 @@
 #include "png_forms.hpp"
 #include "webp_parse.hpp"
 #include "vp8l.hpp"
+#include "vp8.hpp"
 #include "pscan.hpp"
 #include "lscan.hpp"
 #include "resize.hpp"
@@ -125,6 +126,12 @@ DHD ChunkSizes image_chunk_bytes(const ImgDesc& d) {
     z.coef = align16((int64_t)sizeof(Vp8lPlan) + 4 * vp8l_sub_words(d.width, d.height));
     z.binfo = (int64_t)vp8l_groups_cap(d) * (int64_t)sizeof(Vp8lGroup);
     z.plane = align16((int64_t)d.width * d.height * 4 + 64);
+    return chunk_finish(z);
+  }
+  if (kPng && d.kind == kVp8Kind) {  // frame record + coefficients, macroblock records, the Y / U / V planes (the payload is read in place)
+    z.coef = vp8_coef_bytes(d.width, d.height);
+    z.binfo = vp8_binfo_bytes(d.width, d.height);
+    z.plane = vp8_plane_bytes(d.width, d.height);
     return chunk_finish(z);
   }
   // the planes hold a byte per coefficient of the dense int16 layout coef_bytes counts

@@ -90,6 +90,7 @@ class IngestEngine:
         self.png = False  # set_png's choice (False: PNG files report status -1, as any non-JPEG)
         self.png_forms = False  # set_png_forms's choice (False: depths 1 / 2 / 4 / 16 and Adam7 report status 1)
         self.webp = False  # set_webp's choice (False: WebP files report status -1, as any non-JPEG)
+        self.webp_forms = False  # set_webp_forms's choice (False: lossy WebP files report status 1)
         self.draft = 0  # set_draft's choice (0: every JPEG decodes at its coded size)
         self.exif_transpose = False  # set_exif_transpose's choice (False: the Orientation tag is ignored)
 
@@ -195,6 +196,14 @@ class IngestEngine:
         files as status -1: ``fallback.probe_webp`` names them and their workspace bytes."""
         _lib.check(self.lib.dino_ctx_set_webp(self._ctx, int(bool(on))), "dino_ctx_set_webp")
         self.webp = bool(on)
+
+    def set_webp_forms(self, on: bool) -> None:
+        """Decode lossy WebP files (VP8 key frames) as well on this context (``True``; needs
+        ``set_webp(True)``) or leave them declined (``False``, the default) from the next call on
+        (``dino_ctx_set_webp_forms``).  ``fallback.probe_webp_forms`` names them and their
+        workspace bytes."""
+        _lib.check(self.lib.dino_ctx_set_webp_forms(self._ctx, int(bool(on))), "dino_ctx_set_webp_forms")
+        self.webp_forms = bool(on)
 
     def set_draft(self, n: int) -> None:
         """Decode this context's JPEGs of one or three components at the size of Pillow's

@@ -175,6 +175,49 @@ def accept_webp(info: np.ndarray, form: np.ndarray, ws: np.ndarray, webp: str = 
     return out, int(np.asarray(ws, np.int64)[dev].sum()), aws
 
 
+WEBP_FORMS = ("lossless", "all")
+
+
+def check_webp_forms(forms: str, webp: str) -> None:
+    if forms not in WEBP_FORMS:
+        raise ValueError(f"webp_forms must be 'lossless' or 'all', not {forms!r}")
+    if forms == "all" and webp != "device":
+        raise ValueError("webp_forms='all' needs webp='device'")
+
+
+def probe_webp_forms(ptrs: np.ndarray, lens: np.ndarray, max_image_dim: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """``dino_probe_webp_forms`` over images where they lie -> (form int32[B, 3], ws int64[B]).
+    ``form[:, 0]`` is 1 for a lossy WebP that a context with ``dino_ctx_set_webp_forms`` on decodes
+    (``dino_probe_webp`` reports it as form 1), with its width and height in columns 1 and 2 and
+    its exact decode-workspace bytes in ``ws``; 0 for every other file."""
+    p = np.ascontiguousarray(ptrs, np.uint64)
+    n = np.ascontiguousarray(lens, np.int64)
+    flag = np.zeros(len(p), np.uint8)
+    wh = np.zeros((len(p), 2), np.int32)
+    ws = np.zeros(len(p), np.int64)
+    _lib.check(_lib.load().dino_probe_webp_forms(p.ctypes.data_as(ctypes.c_void_p), n.ctypes.data_as(ctypes.c_void_p), len(p),
+                                                 int(max_image_dim), flag.ctypes.data_as(ctypes.c_void_p),
+                                                 wh.ctypes.data_as(ctypes.c_void_p), ws.ctypes.data_as(ctypes.c_void_p)),
+               "dino_probe_webp_forms")
+    return np.concatenate([flag[:, None].astype(np.int32), wh], 1), ws
+
+
+def accept_webp_forms(info: np.ndarray, form: np.ndarray, ws: np.ndarray, cfg=None) -> tuple[np.ndarray, int, int]:
+    """The rows ``accept_webp(.., "device")`` handed to Pillow (status ``IMG_UNSUPPORTED``, kind -1)
+    as a pipeline with ``webp_forms="all"`` treats them: those with ``form[:, 0] == 1`` become
+    status 0, kind 1 with their width and height (decoded on contexts with
+    ``dino_ctx_set_webp_forms`` on and routed like any coefficient-buffer image).  Returns (a copy
+    of info, decode-workspace bytes to add, augment-workspace bytes to add), as ``accept_webp``."""
+    out = np.array(info, np.int32, copy=True)
+    form = np.asarray(form)
+    m = (out[:, 0] == IMG_UNSUPPORTED) & (out[:, 3] == -1) & (form[:, 0] == 1)
+    out[m, 0] = 0
+    out[m, 1:3] = form[m, 1:3]
+    out[m, 3] = KIND_MULTISCAN
+    aws = augment_need(out[m], cfg) if cfg is not None and m.any() else 0
+    return out, int(np.asarray(ws, np.int64)[m].sum()), aws
+
+
 def four_component_mask(info: np.ndarray) -> np.ndarray:
     """Rows of a probed batch that are four-component (CMYK / YCCK) files a context with
     ``dino_ctx_set_four_component`` on decodes (status 1, kind 3)."""

@@ -129,7 +129,8 @@ class MI355XAugPipeline:
                  multiscan_host_max: int | None = None, prefetch: int | None = None,
                  start_host_pool: bool = False, side_ahead: int = 64, resample_filter=None,
                  four_component: str = "host", png: str = "off", jpeg_draft: int = 0,
-                 exif_transpose: bool = False, png_forms: str = "plain", webp: str = "off"):
+                 exif_transpose: bool = False, png_forms: str = "plain", webp: str = "off",
+                 webp_forms: str = "lossless"):
         self._source = source
         # EXIF orientation applied (ImageOps.exif_transpose before convert("RGB")): every slot and
         # side context gets dino_ctx_set_exif_transpose and turns the JPEGs whose tag its walk
@@ -159,6 +160,10 @@ class MI355XAugPipeline:
         # fallback.accept_webp rewrites the rows (_forms)
         fallback.check_webp(webp)
         self._webp = webp
+        # "all": the lossy ones (VP8 key frames) decode on the GPU too (every slot and side context
+        # gets dino_ctx_set_webp_forms; fallback.accept_webp_forms takes their rows back in _forms)
+        fallback.check_webp_forms(webp_forms, webp)
+        self._webp_forms = webp_forms == "all"
         self._aug_cfg = aug_cfg
         # four-component (CMYK / YCCK) JPEGs: "host" hands them to Pillow, "device" decodes them in
         # the kernels (every slot and side context gets dino_ctx_set_four_component) and routes them
@@ -266,6 +271,8 @@ class MI355XAugPipeline:
                 eng.set_png_forms(True)
             if self._webp == "device":
                 eng.set_webp(True)
+            if self._webp_forms:
+                eng.set_webp_forms(True)
             if self._draft:
                 eng.set_draft(self._draft)
             if self._exif:
@@ -472,6 +479,17 @@ class MI355XAugPipeline:
                 dev = int(((form[:, 0] == fallback.WEBP_DEVICE) & (info[:, 0] == 0)).sum())
                 self.stats["webp_device"] += dev
                 self.stats["webp_host"] += int((form[:, 0] != fallback.WEBP_NONE).sum()) - dev
+            if self._webp_forms and (form[:, 0] == fallback.WEBP_DECLINED).any():
+                # webp_forms="all": the lossy files among those just handed to Pillow come back
+                # (fallback.accept_webp_forms), moved from webp_host to webp_device once per batch
+                lossy, need = fallback.probe_webp_forms(ptrs, lens, self._max_image_dim)
+                lossy[form[:, 0] != fallback.WEBP_DECLINED, 0] = 0  # (a skipped image among them)
+                info, extra, extra_aws = fallback.accept_webp_forms(info, lossy, need, cfg)
+                ws, aws = ws + extra, aws + extra_aws
+                if count:
+                    n = int(((lossy[:, 0] == 1) & (info[:, 0] == 0)).sum())
+                    self.stats["webp_device"] += n
+                    self.stats["webp_host"] -= n
         if not self._png_forms or not (info[:, 3] == fallback.KIND_PNG_DECLINED).any():
             return info, ws, aws
         form, need = fallback.probe_png_forms(ptrs, lens, self._max_image_dim)
@@ -655,7 +673,7 @@ class MI355XAugPipeline:
                                                     four_component=self._four_component == "device",
                                                     png=self._png == "device", draft=self._draft,
                                                     exif_transpose=self._exif, png_forms=self._png_forms,
-                                                    webp=self._webp == "device")
+                                                    webp=self._webp == "device", webp_forms=self._webp_forms)
             self.stats["side_lanes"] = lanes
         if pb.jpegs is not None:
             imgs = {int(i): pb.jpegs[i] for i in idx}

@@ -129,7 +129,7 @@ class _SideEngine:
     def __init__(self, device: torch.device, max_images: int, max_image_dim: int, cu_count: int = 0,
                  dedicated: bool = True, index: int = 0, stream_set: int = 0, lanes: bool = False,
                  four_component: bool = False, png: bool = False, draft: int = 0, exif_transpose: bool = False,
-                 png_forms: bool = False, webp: bool = False):
+                 png_forms: bool = False, webp: bool = False, webp_forms: bool = False):
         self.raw = _create_stream(device.index or 0, int(cu_count)) if dedicated else None
         self.stream = self.raw if dedicated else role_stream(device, "side", index, stream_set)
         self.eng = IngestEngine(device, max_batch=max_images, max_views=1, max_crop_size=8,
@@ -143,6 +143,8 @@ class _SideEngine:
                 self.eng.set_png_forms(True)
         if webp:  # lossless WebP files join the pools as well
             self.eng.set_webp(True)
+            if webp_forms:  # and the lossy ones
+                self.eng.set_webp_forms(True)
         if draft:  # the containers then hold the scaled images, as the batches' own contexts decode them
             self.eng.set_draft(draft)
         if exif_transpose:  # the containers then hold the upright images, which the batches' contexts do not turn again
@@ -207,7 +209,7 @@ class DeviceSideDecoder:
     def __init__(self, device: torch.device, max_images: int = WAVE_POOL, min_images: int | None = None,
                  engines: int | None = None, max_image_dim: int = 0, stream_set: int = 0, lanes: bool = False,
                  four_component: bool = False, png: bool = False, draft: int = 0, exif_transpose: bool = False,
-                 png_forms: bool = False, webp: bool = False):
+                 png_forms: bool = False, webp: bool = False, webp_forms: bool = False):
         import os
         # measured (scripts/route_study.py, 16 progressive per 256-image batch, dedicated queues,
         # look-ahead 64, profiles/r03_side_pools.jsonl): pools of 16 images on 2 contexts 11.2k img/s,
@@ -234,6 +236,7 @@ class DeviceSideDecoder:
         self.exif_transpose = bool(exif_transpose)  # the pipeline's exif_transpose
         self.png_forms = bool(png_forms) and self.png  # the pipeline's png_forms == "all"
         self.webp = bool(webp)                      # the pipeline's webp == "device"
+        self.webp_forms = bool(webp_forms) and self.webp  # the pipeline's webp_forms == "all"
         self.lane_min = int(os.environ.get("DINO_SIDE_LANE_MIN", LANE_MIN_POOL))  # smaller pools: wave decoder
         self._engines: list[_SideEngine] = []
         self._rr = 0
@@ -281,7 +284,8 @@ class DeviceSideDecoder:
             e = _SideEngine(self.device, self.max_images, self.max_image_dim, self.cu_count, self.dedicated,
                             index=len(self._engines), stream_set=self.stream_set, lanes=self.lanes,
                             four_component=self.four_component, png=self.png, draft=self.draft,
-                            exif_transpose=self.exif_transpose, png_forms=self.png_forms, webp=self.webp)
+                            exif_transpose=self.exif_transpose, png_forms=self.png_forms, webp=self.webp,
+                            webp_forms=self.webp_forms)
             self._engines.append(e)
             return e
         e = self._engines[self._rr % len(self._engines)]
@@ -348,6 +352,11 @@ class DeviceSideDecoder:
             form, need = fallback.probe_webp(hb.data_ptr() + o[:-1], np.diff(o), self.max_image_dim)
             info, extra, _ = fallback.accept_webp(info, form, need, "device")
             ws += extra
+            if self.webp_forms:  # and the lossy ones among those it declined
+                lossy, need = fallback.probe_webp_forms(hb.data_ptr() + o[:-1], np.diff(o), self.max_image_dim)
+                lossy[form[:, 0] != fallback.WEBP_DECLINED, 0] = 0
+                info, extra, _ = fallback.accept_webp_forms(info, lossy, need)
+                ws += extra
         if self.exif_transpose:  # the second RGB region of each image the context turns (upright sizes in info)
             o = off.numpy()
             info, extra, _ = fallback.accept_orient(info, fallback.probe_orient(hb.data_ptr() + o[:-1], np.diff(o)))

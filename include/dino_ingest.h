@@ -58,7 +58,9 @@
  *    dino_orient_tile and dino_kernel_times ids 27 and 28; dino_ctx_set_png_forms (PNG bit
  *    depths 1, 2, 4 and 16 and Adam7 decoded on the device, off by default),
  *    dino_probe_png_forms and dino_debug_png_forms_decode; dino_ctx_set_webp (lossless WebP
- *    decoded on the device, off by default), dino_probe_webp and dino_debug_webp_decode.
+ *    decoded on the device, off by default), dino_probe_webp and dino_debug_webp_decode;
+ *    dino_ctx_set_webp_forms (lossy WebP decoded on the device, off by default),
+ *    dino_probe_webp_forms and dino_debug_vp8_decode.
  */
 #ifndef DINO_INGEST_H
 #define DINO_INGEST_H
@@ -442,6 +444,37 @@ int dino_probe_webp(const uint64_t* ptrs, const int64_t* lens, int32_t batch, in
  * ARGB plane, RGB region, groups the code region holds}. */
 int dino_debug_webp_decode(const uint8_t* bytes, int64_t len, int32_t max_image_dim, uint8_t* rgb, int64_t rgb_cap,
                            int32_t* info, int64_t* layout);
+
+/* Lossy WebP on this ctx, from the next call on: 0 (default) leaves the files below declined
+ * (DINO_IMG_UNSUPPORTED, as dino_ctx_set_webp alone reports them); non-zero decodes them bit for
+ * bit as Pillow 12's Image.open(..).convert("RGB") (libwebp's fancy upsampler, no dithering):
+ * RIFF / WEBP holding one "VP8 " chunk, alone or in a VP8X container whose canvas is the frame's,
+ * without ALPH, ANIM / ANMF or EXIF chunks; a shown key frame with the start code 9d 01 2a whose
+ * first partition ends inside the chunk; one token partition and use_lf_delta = 0 in the frame
+ * header (other values: DINO_IMG_UNSUPPORTED).  A partition that ends before the last macroblock,
+ * on which Pillow raises, is DINO_IMG_CORRUPT.  Needs dino_ctx_set_webp on (DINO_EINVAL
+ * otherwise); turning that off suspends this.  The kernels are timed under dino_kernel_times
+ * id 23 ("k_png"). */
+int dino_ctx_set_webp_forms(dino_ctx* ctx, int32_t on);
+
+/* Which of the files dino_probe_webp reports as form 1 such a ctx decodes (no GPU involved):
+ * form[i] = 1 with wh[2 i], wh[2 i + 1] = width, height and ws_need[i] = the exact
+ * decode-workspace bytes of image i, else 0.  The container walk, the frame tag and the
+ * bool-coded frame header (read here on the host) decide.  ptrs: absolute host addresses. */
+int dino_probe_webp_forms(const uint64_t* ptrs, const int64_t* lens, int32_t batch, int32_t max_image_dim,
+                          uint8_t* form, int32_t* wh, int64_t* ws_need);
+
+/* Debug: the host model of that decode (the text the kernels compile, run with one lane).
+ * info = {status, width, height, form, then the coverage record as bit masks: 16x16 modes seen
+ * (bit: 0 DC, 1 TM, 2 V, 3 H), sub-block modes (bits 0..9: DC TM VE HE RD VR LD VL HD HU), chroma
+ * modes, filter type (bit: 0 none, 1 simple, 2 complex), hev thresholds of filtered macroblocks
+ * (bits 0..2), segments (bit 0 off, bit 1 on), a skipped macroblock, extra-bit categories (bit
+ * c - 3 for category c = 3..6)}: 12 values; status is DINO_IMG_CORRUPT and the rest 0 unless
+ * dino_probe_webp_forms says 1; rgb receives 3 w h bytes when status is 0 (rgb_cap too small:
+ * DINO_IMG_NO_SPACE).  layout = {chunk bytes, frame record + coefficients, macroblock records,
+ * Y / U / V planes, RGB region}. */
+int dino_debug_vp8_decode(const uint8_t* bytes, int64_t len, int32_t max_image_dim, uint8_t* rgb, int64_t rgb_cap,
+                          int32_t* info, int64_t* layout);
 
 /* Reduced-size JPEG decode on this ctx, from the next call on: n = 0 (default) decodes every
  * image at its coded size; n > 0 decodes each JPEG of one or three components as
