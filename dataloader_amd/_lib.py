@@ -108,6 +108,9 @@ def load() -> ctypes.CDLL:
         "dino_ctx_set_webp_forms": (i32, [vp, i32]),
         "dino_probe_webp_forms": (i32, [vp, vp, i32, i32, vp, vp, vp]),
         "dino_debug_vp8_decode": (i32, [vp, i64, i32, vp, i64, vp, vp]),
+        "dino_ctx_set_gif": (i32, [vp, i32]),
+        "dino_probe_gif": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+        "dino_debug_gif_decode": (i32, [vp, i64, i32, vp, i64, vp, vp]),
         "dino_ctx_set_exif_transpose": (i32, [vp, i32]),
         "dino_probe_orient": (i32, [vp, vp, i32, vp]),
         "dino_orient_map": (i32, [i32, i32, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
@@ -159,4 +162,5 @@ def exported_symbols() -> list[str]:
             "dino_ctx_set_draft", "dino_ctx_set_exif_transpose", "dino_probe_orient", "dino_orient_map",
             "dino_orient_tile", "dino_ctx_set_png_forms", "dino_probe_png_forms", "dino_debug_png_forms_decode",
             "dino_ctx_set_webp", "dino_probe_webp", "dino_debug_webp_decode",
-            "dino_ctx_set_webp_forms", "dino_probe_webp_forms", "dino_debug_vp8_decode"]
+            "dino_ctx_set_webp_forms", "dino_probe_webp_forms", "dino_debug_vp8_decode",
+            "dino_ctx_set_gif", "dino_probe_gif", "dino_debug_gif_decode"]

@@ -124,7 +124,7 @@ class MI355XBackend:
                  side_ahead: int | None = None, resample_filter: str | None = None,
                  four_component: str = "host", png: str = "off", jpeg_draft: int = 0,
                  exif_transpose: bool = False, png_forms: str = "plain",
-                 webp: str = "off", webp_forms: str = "lossless") -> None:
+                 webp: str = "off", webp_forms: str = "lossless", gif: str = "off") -> None:
         # Pillow filter of every resize: None = bicubic everywhere (CPUBackend parity, which
         # ignores EvalAugSpec.interpolation too); a filter's name applies to every recipe;
         # "spec" honours EvalAugSpec.interpolation as the reference's GPU peer does
@@ -166,6 +166,13 @@ class MI355XBackend:
         from .fallback import check_webp_forms
         check_webp_forms(webp_forms, webp)
         self._webp_forms = webp_forms
+        # GIF files: "off" (default) leaves them zero-filled with status -1, as any non-JPEG; "host"
+        # hands every GIF to Pillow; "device" decodes frame 0 of the files whose header the probe
+        # verifies in the kernels (k_gifwalk, k_giflzw, k_gif_rgb) and hands the rest to Pillow.
+        # The UserAugSpec pipeline hands every GIF over under both
+        from .fallback import check_gif
+        check_gif(gif)
+        self._gif = gif
         # reduced-size JPEG decode, off at 0: N > 0 decodes every JPEG as Pillow does after
         # im.draft("RGB", (N, N)) (1/2, 1/4 or 1/8 of the coded size where both sides stay >= N;
         # fallback.draft_scale), on the device (libjpeg's reduced inverse DCTs) and in every
@@ -289,7 +296,7 @@ class MI355XBackend:
             return MI355XUserAugPipeline(source, aug_spec, getattr(source, "_batch_size", 1),
                                          out_dtype=pipeline_cfg.output_dtype, device=pipeline_cfg.device_id,
                                          max_image_dim=self._max_image_dim, workspace_bytes=self._workspace_bytes,
-                                         norm=norm, resample_filter=self.spec_filter(aug_spec), png=self._png, webp=self._webp,
+                                         norm=norm, resample_filter=self.spec_filter(aug_spec), png=self._png, webp=self._webp, gif=self._gif,
                                          jpeg_draft=self._jpeg_draft, exif_transpose=self._exif_transpose)
         if _is_dinov2_spec(aug_spec):
             aug_cfg = aug_spec.aug_cfg
@@ -340,6 +347,7 @@ class MI355XBackend:
             png_forms=self._png_forms,
             webp=self._webp,
             webp_forms=self._webp_forms,
+            gif=self._gif,
         )
 
     def build_pipeline_iterator(self, pipeline: Any, aug_spec: Any, output_map: list[str],

@@ -18,6 +18,7 @@
 #include <hip/hip_ext.h>
 
 #include "exif_parse.hpp"
+#include "gif_lzw.hpp"
 #include "hostcopy.hpp"
 #include "inflate.hpp"
 #include "jpeg_parse.hpp"
@@ -70,6 +71,7 @@ struct dino_ctx {
   int32_t png_forms = 0;      // dino_ctx_set_png_forms: read at each decode launch
   int32_t webp = 0;           // dino_ctx_set_webp: read at each decode launch
   int32_t webp_forms = 0;     // dino_ctx_set_webp_forms: read at each decode launch
+  int32_t gif = 0;            // dino_ctx_set_gif: read at each decode launch
   int32_t draft = 0;          // dino_ctx_set_draft: read at each decode launch
   int32_t exif_transpose = 0; // dino_ctx_set_exif_transpose: read at each decode launch
   OCtl* d_octl = nullptr;     // k_orient's tiles (allocated by the first dino_ctx_set_exif_transpose(ctx, 1))
@@ -159,7 +161,7 @@ int dino_decode_spans(dino_ctx* c, const uint8_t* d_bytes, const int64_t* d_offs
   hipStream_t s = (hipStream_t)stream;
   DecodeArgs a{d_bytes, d_offsets, d_lengths, d_raw_mask, batch, c->lim.max_image_dim, c->d_desc, c->d_ws,
                c->ws_size, c->geom, c->d_pctl, c->four_component, c->png, c->png && c->png_forms, c->webp,
-               c->webp && c->webp_forms, c->draft,
+               c->webp && c->webp_forms, c->gif, c->draft,
                c->exif_transpose ? c->d_octl : nullptr};
   hipError_t e = launch_decode(a, s, c->tm());
   if (e != hipSuccess) return hip_fail(e, "dino_decode");
@@ -897,6 +899,69 @@ int dino_debug_webp_decode(const uint8_t* p, int64_t len, int32_t max_image_dim,
   int st = DINO_IMG_CORRUPT;
   webp_host(p, len, max_image_dim, &d, rgb, &st, info + 4);
   info[0] = st;
+  return DINO_OK;
+}
+
+int dino_ctx_set_gif(dino_ctx* c, int32_t on) {
+  if (!c) return fail(DINO_EINVAL, "dino_ctx_set_gif: null ctx%s%lld");
+  c->gif = on != 0;  // read at each launch (launch_decode)
+  return DINO_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// The form dino_probe_gif states: 0 not a GIF (or one with a zero side, on which Pillow raises at
+// open: it stays DINO_IMG_CORRUPT), 1 a GIF Pillow decides, 2 one the device decodes (d: its
+// kind-8 descriptor, status OK; a side above max_image_dim is DINO_IMG_LIMIT: Pillow's).
+int gif_form(const uint8_t* p, int64_t len, int32_t max_image_dim, ImgDesc* d) {
+  if (max_image_dim <= 0 || max_image_dim > kMaxImageDim) max_image_dim = kMaxImageDim;
+  d->kind = 0;
+  d->width = d->height = 0;
+  d->coef_bytes = 0;
+  d->status = DINO_IMG_CORRUPT;
+  if (!gif_signature(p, len)) return 0;
+  const int st = parse_gif_head(p, len, max_image_dim, d);
+  return st == DINO_IMG_OK ? 2 : st == DINO_IMG_CORRUPT ? 0 : 1;
+}
+}  // namespace
+
+extern "C" {
+
+int dino_probe_gif(const uint64_t* ptrs, const int64_t* lens, int32_t batch, int32_t max_image_dim, uint8_t* form,
+                   int32_t* wh, int64_t* ws_need) {
+  if (batch < 0 || (batch > 0 && (!ptrs || !lens || !form || !wh || !ws_need)))
+    return fail(DINO_EINVAL, "dino_probe_gif: bad arguments%s%lld");
+  for (int32_t i = 0; i < batch; ++i) {
+    ImgDesc d;
+    form[i] = 0;
+    wh[2 * i] = wh[2 * i + 1] = 0;
+    ws_need[i] = 0;
+    if (lens[i] <= 0) continue;
+    form[i] = (uint8_t)gif_form((const uint8_t*)(uintptr_t)ptrs[i], lens[i], max_image_dim, &d);
+    if (form[i] != 2) continue;
+    wh[2 * i] = d.width, wh[2 * i + 1] = d.height;
+    ws_need[i] = image_chunk_bytes(d).total();
+  }
+  return DINO_OK;
+}
+
+int dino_debug_gif_decode(const uint8_t* p, int64_t len, int32_t max_image_dim, uint8_t* rgb, int64_t rgb_cap,
+                          int32_t* info, int64_t* layout) {
+  if (!p || len <= 0 || !info || !layout || !rgb) return fail(DINO_EINVAL, "dino_debug_gif_decode: bad arguments%s%lld");
+  ImgDesc d;
+  for (int k = 0; k < 8; ++k) info[k] = 0;
+  for (int k = 0; k < 5; ++k) layout[k] = 0;
+  info[0] = DINO_IMG_CORRUPT;
+  if (gif_form(p, len, max_image_dim, &d) != 2) return DINO_OK;
+  info[1] = d.width, info[2] = d.height, info[3] = 2;
+  info[4] = d.color, info[5] = d.mcus_y, info[6] = d.n_scans;
+  const ChunkSizes z = image_chunk_bytes(d);
+  layout[0] = z.total(), layout[1] = z.ent, layout[2] = z.plane, layout[3] = z.htab, layout[4] = z.rgb;
+  if ((int64_t)d.width * d.height * 3 > rgb_cap) return (info[0] = DINO_IMG_NO_SPACE, DINO_OK);
+  std::vector<uint32_t> ent((size_t)z.ent / 4 + 1);
+  std::vector<uint8_t> plane((size_t)z.plane), pal(kGifPalBytes);
+  info[0] = gif_decode_host(p, len, d, (uint8_t*)ent.data(), plane.data(), pal.data(), rgb);
   return DINO_OK;
 }
 

@@ -31,6 +31,7 @@
 //   kernels_png_forms.inc           k_pnghead_forms, k_unfilter_forms: depths 1 / 2 / 4 / 16 and Adam7 (opt-in)
 //   kernels_webp.inc                k_webphead, k_vp8l, k_vp8l_inv: lossless WebP (opt-in)
 //   kernels_vp8.inc                 k_vp8head, k_vp8_tok, k_vp8_rec, k_vp8_rgb: lossy WebP (opt-in)
+//   kernels_gif.inc                 k_gifhead, k_gifwalk, k_giflzw, k_gif_rgb: GIF (opt-in)
 //   kernels_draft.inc               k_draft, k_idct_red, k_color_red: reduced-size JPEG decode (opt-in)
 //   kernels_orient.inc              k_exif, k_orient_scan, k_orient, k_orient_done: EXIF orientation applied (opt-in)
 //   kernels_launch.inc              host: init_launch_geom and every launch_*; k_pixel_ops
@@ -53,6 +54,7 @@
 #include "png_forms.hpp"
 #include "webp_parse.hpp"
 #include "vp8l.hpp"
+#include "gif_lzw.hpp"
 #include "inflate.hpp"
 #include "sampler.hpp"
 
@@ -3524,6 +3526,7 @@ __global__ void __launch_bounds__(kVFinalThreads) k_vfinal(const ImgDesc* __rest
 #include "kernels_png_forms.inc"
 #include "kernels_webp.inc"
 #include "kernels_vp8.inc"
+#include "kernels_gif.inc"
 #include "kernels_draft.inc"
 #include "kernels_orient.inc"
 #include "kernels_launch.inc"

@@ -107,6 +107,7 @@ struct DecodeArgs {
   int32_t png_forms;        // 1: so do the PNG forms of png_forms.hpp (dino_ctx_set_png_forms; needs png), 0: they stay declined
   int32_t webp;             // 1: lossless WebP files decode (dino_ctx_set_webp), 0: DINO_IMG_CORRUPT as any non-JPEG
   int32_t webp_forms;       // 1: so do lossy WebP files (dino_ctx_set_webp_forms; needs webp), 0: they stay declined
+  int32_t gif;              // 1: GIF files decode (dino_ctx_set_gif), 0: DINO_IMG_CORRUPT as any non-JPEG
   int32_t draft;            // N > 0: JPEGs decode at Pillow's draft("RGB", (N, N)) size (dino_ctx_set_draft), 0: full size
   OCtl* octl;               // non-null: JPEGs leave the decode upright (dino_ctx_set_exif_transpose), null: as coded
 };

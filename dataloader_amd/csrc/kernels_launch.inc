@@ -109,6 +109,8 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
   if (a.webp) TIMED(tm, kKPng, s, (k_webphead<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.max_dim, a.desc)));
   // a context with dino_ctx_set_webp_forms on: the lossy files k_webphead declined get theirs
   if (a.webp && a.webp_forms) TIMED(tm, kKPng, s, (k_vp8head<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.max_dim, a.desc)));
+  // a context with dino_ctx_set_gif on: GIF files get their descriptor before the plan
+  if (a.gif) TIMED(tm, kKPng, s, (k_gifhead<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.max_dim, a.desc)));
   // a context with dino_ctx_set_draft on: the JPEGs that scale get their reduced size before the plan
   if (a.draft > 0) TIMED(tm, kKDraft, s, (k_draft<<<(B + 63) / 64, 64, 0, s>>>(a.desc, B, a.draft)));
   // a context with dino_ctx_set_exif_transpose on: every image gets its orientation before the plan
@@ -116,9 +118,9 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
     TIMED(tm, kKExif, s, (k_exif<<<(B + 63) / 64, 64, 0, s>>>(a.bytes, a.offsets, a.lengths, a.raw_mask, B, a.desc)));
     TIMED(tm, kKExif, s, (k_orient_scan<<<1, 1024, 0, s>>>(a.desc, B, a.octl)));
   }
-  // (k_plan<true> also sizes kind-4 and kind-6 images; without the options there is none and k_plan<false> is the
+  // (k_plan<true> also sizes kind-4, kind-6, kind-7 and kind-8 images; without the options there is none and k_plan<false> is the
   // code it was; k_plan<.., true> gives the images that turn their second RGB region)
-  const bool sized = a.png || a.webp;
+  const bool sized = a.png || a.webp || a.gif;
   if (a.octl && sized) TIMED(tm, kKPlan, s, (k_plan<true, true><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
   else if (a.octl) TIMED(tm, kKPlan, s, (k_plan<false, true><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
   else if (sized) TIMED(tm, kKPlan, s, (k_plan<true><<<1, 1024, 0, s>>>(a.desc, B, a.ws_size, a.pctl)));
@@ -163,6 +165,11 @@ hipError_t launch_decode(const DecodeArgs& a, hipStream_t s, KernelTimer* tm) {
     TIMED(tm, kKPng, s, (k_vp8_tok<<<B, 64, 0, s>>>(a.bytes, a.offsets, a.desc, a.ws)));
     TIMED(tm, kKPng, s, (k_vp8_rec<<<B, kVp8RecThreads, 0, s>>>(a.desc, a.ws)));
     TIMED(tm, kKPng, s, (k_vp8_rgb<<<dim3(kVp8RgbWgs, B), 256, 0, s>>>(a.desc, a.ws)));
+  }
+  if (a.gif) {  // GIF images (kind 8): no other context has one
+    TIMED(tm, kKPng, s, (k_gifwalk<<<B, kGifWalkThreads, 0, s>>>(a.bytes, a.offsets, a.lengths, a.desc, a.ws)));
+    TIMED(tm, kKPng, s, (k_giflzw<<<B, 64, 0, s>>>(a.desc, a.ws)));
+    TIMED(tm, kKPng, s, (k_gif_rgb<<<dim3(kGifRgbWgs, B), 256, 0, s>>>(a.desc, a.ws)));
   }
   if (a.octl) {  // after every colour stage: the images k_exif tagged turn, then show their upright side
     TIMED(tm, kKOrient, s, (k_orient<<<a.geom.grid_or, 256, 0, s>>>(a.desc, a.ws, a.octl, B)));

@@ -10,6 +10,7 @@
 #include "webp_parse.hpp"
 #include "vp8l.hpp"
 #include "vp8.hpp"
+#include "gif_parse.hpp"
 #include "pscan.hpp"
 #include "lscan.hpp"
 #include "resize.hpp"
@@ -103,7 +104,7 @@ DHD int vp8l_groups_cap(const ImgDesc& d) {
   return px < kVp8lMaxGroups ? (int)px : kVp8lMaxGroups;
 }
 
-// kPng: the caller may hold PNG images (kind 4) or lossless WebP images (kind 6).  k_plan of a context without dino_ctx_set_png is
+// kPng: the caller may hold PNG images (kind 4), WebP images (kinds 6 and 7) or GIF images (kind 8).  k_plan of a context without dino_ctx_set_png is
 // instantiated without them and stays the code it was.  kOrient: the caller's k_exif wrote every
 // image's orientation (dino_ctx_set_exif_transpose); without it pad0 is not read and the layout
 // is the one it was.
@@ -132,6 +133,12 @@ DHD ChunkSizes image_chunk_bytes(const ImgDesc& d) {
     z.coef = vp8_coef_bytes(d.width, d.height);
     z.binfo = vp8_binfo_bytes(d.width, d.height);
     z.plane = vp8_plane_bytes(d.width, d.height);
+    return chunk_finish(z);
+  }
+  if (kPng && d.kind == kGifKind) {  // the joined LZW stream, the colour indices in coded row order, the colour table
+    z.ent = align16((int64_t)d.scan_len + 64);
+    z.plane = align16((int64_t)d.width * d.height + 64);
+    z.htab = kGifPalBytes;
     return chunk_finish(z);
   }
   // the planes hold a byte per coefficient of the dense int16 layout coef_bytes counts

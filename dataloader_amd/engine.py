@@ -91,6 +91,7 @@ class IngestEngine:
         self.png_forms = False  # set_png_forms's choice (False: depths 1 / 2 / 4 / 16 and Adam7 report status 1)
         self.webp = False  # set_webp's choice (False: WebP files report status -1, as any non-JPEG)
         self.webp_forms = False  # set_webp_forms's choice (False: lossy WebP files report status 1)
+        self.gif = False  # set_gif's choice (False: GIF files report status -1, as any non-JPEG)
         self.draft = 0  # set_draft's choice (0: every JPEG decodes at its coded size)
         self.exif_transpose = False  # set_exif_transpose's choice (False: the Orientation tag is ignored)
 
@@ -204,6 +205,15 @@ class IngestEngine:
         workspace bytes."""
         _lib.check(self.lib.dino_ctx_set_webp_forms(self._ctx, int(bool(on))), "dino_ctx_set_webp_forms")
         self.webp_forms = bool(on)
+
+    def set_gif(self, on: bool) -> None:
+        """Decode GIF files (frame 0 of a file whose first frame covers the screen and has a
+        colour table) on this context (``True``) or report every GIF ``DINO_IMG_CORRUPT``
+        (``False``, the default) from the next call on (``dino_ctx_set_gif``).  The probes keep
+        reporting these files as status -1: ``fallback.probe_gif`` names them and their
+        workspace bytes."""
+        _lib.check(self.lib.dino_ctx_set_gif(self._ctx, int(bool(on))), "dino_ctx_set_gif")
+        self.gif = bool(on)
 
     def set_draft(self, n: int) -> None:
         """Decode this context's JPEGs of one or three components at the size of Pillow's

@@ -175,6 +175,57 @@ def accept_webp(info: np.ndarray, form: np.ndarray, ws: np.ndarray, webp: str = 
     return out, int(np.asarray(ws, np.int64)[dev].sum()), aws
 
 
+GIF_MODES = ("off", "host", "device")
+GIF_NONE, GIF_DECLINED, GIF_DEVICE = 0, 1, 2  # dino_probe_gif's forms
+
+
+def check_gif(mode: str) -> None:
+    if mode not in GIF_MODES:
+        raise ValueError(f"gif must be 'off', 'host' or 'device', not {mode!r}")
+
+
+def probe_gif(ptrs: np.ndarray, lens: np.ndarray, max_image_dim: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """``dino_probe_gif`` over images where they lie (absolute host addresses + lengths) ->
+    (form int32[B, 3], ws int64[B]).  ``form[:, 0]`` is 0 for a file that is no GIF, 1 for a GIF a
+    context with ``dino_ctx_set_gif`` on does not decode (no colour table, a frame that is not the
+    screen, an unverified header: Pillow decides it) and 2 for a GIF it decodes, with the image's
+    width and height in columns 1 and 2 and its decode-workspace bytes in ``ws``."""
+    p = np.ascontiguousarray(ptrs, np.uint64)
+    n = np.ascontiguousarray(lens, np.int64)
+    flag = np.zeros(len(p), np.uint8)
+    wh = np.zeros((len(p), 2), np.int32)
+    ws = np.zeros(len(p), np.int64)
+    _lib.check(_lib.load().dino_probe_gif(p.ctypes.data_as(ctypes.c_void_p), n.ctypes.data_as(ctypes.c_void_p), len(p),
+                                          int(max_image_dim), flag.ctypes.data_as(ctypes.c_void_p),
+                                          wh.ctypes.data_as(ctypes.c_void_p), ws.ctypes.data_as(ctypes.c_void_p)),
+               "dino_probe_gif")
+    return np.concatenate([flag[:, None].astype(np.int32), wh], 1), ws
+
+
+def accept_gif(info: np.ndarray, form: np.ndarray, ws: np.ndarray, gif: str = "device",
+               cfg=None) -> tuple[np.ndarray, int, int]:
+    """The probe's info (status -1, kind -1 for every GIF) as a pipeline with the option ``gif``
+    treats the batch, as ``accept_webp`` does for WebP.  ``"device"``: rows with ``form[:, 0] == 2``
+    become status 0, kind 1 with their width and height (decoded on contexts with
+    ``dino_ctx_set_gif`` on and routed like any coefficient-buffer image), rows with form 1 status
+    ``IMG_UNSUPPORTED`` (handed to Pillow).  ``"host"``: both become ``IMG_UNSUPPORTED``.
+    ``"off"``: nothing changes.  Returns (a copy of info, decode-workspace bytes to add,
+    augment-workspace bytes to add): the probe counted neither."""
+    check_gif(gif)
+    out = np.array(info, np.int32, copy=True)
+    if gif == "off":
+        return out, 0, 0
+    form = np.asarray(form)
+    mine = (out[:, 0] == IMG_CORRUPT) & (out[:, 3] == -1)
+    dev = mine & (form[:, 0] == GIF_DEVICE) & (gif == "device")
+    out[mine & (form[:, 0] != GIF_NONE) & ~dev, 0] = IMG_UNSUPPORTED
+    out[dev, 0] = 0
+    out[dev, 1:3] = form[dev, 1:3]
+    out[dev, 3] = KIND_MULTISCAN
+    aws = augment_need(out[dev], cfg) if cfg is not None and dev.any() else 0
+    return out, int(np.asarray(ws, np.int64)[dev].sum()), aws
+
+
 WEBP_FORMS = ("lossless", "all")
 
 

@@ -130,7 +130,7 @@ class MI355XAugPipeline:
                  start_host_pool: bool = False, side_ahead: int = 64, resample_filter=None,
                  four_component: str = "host", png: str = "off", jpeg_draft: int = 0,
                  exif_transpose: bool = False, png_forms: str = "plain", webp: str = "off",
-                 webp_forms: str = "lossless"):
+                 webp_forms: str = "lossless", gif: str = "off"):
         self._source = source
         # EXIF orientation applied (ImageOps.exif_transpose before convert("RGB")): every slot and
         # side context gets dino_ctx_set_exif_transpose and turns the JPEGs whose tag its walk
@@ -164,6 +164,10 @@ class MI355XAugPipeline:
         # gets dino_ctx_set_webp_forms; fallback.accept_webp_forms takes their rows back in _forms)
         fallback.check_webp_forms(webp_forms, webp)
         self._webp_forms = webp_forms == "all"
+        # GIF files: the same three modes ("device": every slot and side context gets dino_ctx_set_gif and
+        # decodes the files dino_probe_gif verifies; fallback.accept_gif rewrites the rows in _forms)
+        fallback.check_gif(gif)
+        self._gif = gif
         self._aug_cfg = aug_cfg
         # four-component (CMYK / YCCK) JPEGs: "host" hands them to Pillow, "device" decodes them in
         # the kernels (every slot and side context gets dino_ctx_set_four_component) and routes them
@@ -204,7 +208,7 @@ class MI355XAugPipeline:
         # four_component: CMYK / YCCK images kept on the device (four_component="device")
         self.stats = {"batches": 0, "images": 0, "status": Counter(), "host_decoded": 0, "reserves": 0,
                       "side_decoded": 0, "four_component": 0, "png_device": 0, "png_host": 0,
-                      "webp_device": 0, "webp_host": 0}
+                      "webp_device": 0, "webp_host": 0, "gif_device": 0, "gif_host": 0}
         if self._exif:  # images the contexts turned / images handed to Pillow because the walk verified nothing
             self.stats.update(orient_device=0, orient_host=0)
         # host-side seconds per phase: pull / pack / probe (host half), wait (launch thread
@@ -273,6 +277,8 @@ class MI355XAugPipeline:
                 eng.set_webp(True)
             if self._webp_forms:
                 eng.set_webp_forms(True)
+            if self._gif == "device":
+                eng.set_gif(True)
             if self._draft:
                 eng.set_draft(self._draft)
             if self._exif:
@@ -468,7 +474,18 @@ class MI355XAugPipeline:
         ``png_host`` to ``png_device`` in ``stats`` once per batch.  ``skip``: images already
         handed over.  Returns (info, ws, aws).  With ``webp`` on, the WebP rows come first
         (``fallback.accept_webp``: the lossless files become coefficient-buffer images with their
-        workspace and view scratch, the others go to Pillow), counted as ``webp_device`` / ``webp_host``."""
+        workspace and view scratch, the others go to Pillow), counted as ``webp_device`` / ``webp_host``;
+        with ``gif`` on the GIF rows the same way (``fallback.accept_gif``, ``gif_device`` / ``gif_host``)."""
+        if self._gif != "off" and ((info[:, 0] == fallback.IMG_CORRUPT) & (info[:, 3] == -1)).any():
+            form, need = fallback.probe_gif(ptrs, lens, self._max_image_dim)
+            for i in skip:
+                form[int(i), 0] = 0
+            info, extra, extra_aws = fallback.accept_gif(info, form, need, self._gif, cfg)
+            ws, aws = ws + extra, aws + extra_aws
+            if count:
+                dev = int(((form[:, 0] == fallback.GIF_DEVICE) & (info[:, 0] == 0)).sum())
+                self.stats["gif_device"] += dev
+                self.stats["gif_host"] += int((form[:, 0] != fallback.GIF_NONE).sum()) - dev
         if self._webp != "off" and ((info[:, 0] == fallback.IMG_CORRUPT) & (info[:, 3] == -1)).any():
             form, need = fallback.probe_webp(ptrs, lens, self._max_image_dim)
             for i in skip:
@@ -673,7 +690,8 @@ class MI355XAugPipeline:
                                                     four_component=self._four_component == "device",
                                                     png=self._png == "device", draft=self._draft,
                                                     exif_transpose=self._exif, png_forms=self._png_forms,
-                                                    webp=self._webp == "device", webp_forms=self._webp_forms)
+                                                    webp=self._webp == "device", webp_forms=self._webp_forms,
+                                                    gif=self._gif == "device")
             self.stats["side_lanes"] = lanes
         if pb.jpegs is not None:
             imgs = {int(i): pb.jpegs[i] for i in idx}

@@ -129,7 +129,8 @@ class _SideEngine:
     def __init__(self, device: torch.device, max_images: int, max_image_dim: int, cu_count: int = 0,
                  dedicated: bool = True, index: int = 0, stream_set: int = 0, lanes: bool = False,
                  four_component: bool = False, png: bool = False, draft: int = 0, exif_transpose: bool = False,
-                 png_forms: bool = False, webp: bool = False, webp_forms: bool = False):
+                 png_forms: bool = False, webp: bool = False, webp_forms: bool = False,
+                 gif: bool = False):
         self.raw = _create_stream(device.index or 0, int(cu_count)) if dedicated else None
         self.stream = self.raw if dedicated else role_stream(device, "side", index, stream_set)
         self.eng = IngestEngine(device, max_batch=max_images, max_views=1, max_crop_size=8,
@@ -145,6 +146,8 @@ class _SideEngine:
             self.eng.set_webp(True)
             if webp_forms:  # and the lossy ones
                 self.eng.set_webp_forms(True)
+        if gif:  # GIF files join the pools as well
+            self.eng.set_gif(True)
         if draft:  # the containers then hold the scaled images, as the batches' own contexts decode them
             self.eng.set_draft(draft)
         if exif_transpose:  # the containers then hold the upright images, which the batches' contexts do not turn again
@@ -209,7 +212,8 @@ class DeviceSideDecoder:
     def __init__(self, device: torch.device, max_images: int = WAVE_POOL, min_images: int | None = None,
                  engines: int | None = None, max_image_dim: int = 0, stream_set: int = 0, lanes: bool = False,
                  four_component: bool = False, png: bool = False, draft: int = 0, exif_transpose: bool = False,
-                 png_forms: bool = False, webp: bool = False, webp_forms: bool = False):
+                 png_forms: bool = False, webp: bool = False, webp_forms: bool = False,
+                 gif: bool = False):
         import os
         # measured (scripts/route_study.py, 16 progressive per 256-image batch, dedicated queues,
         # look-ahead 64, profiles/r03_side_pools.jsonl): pools of 16 images on 2 contexts 11.2k img/s,
@@ -237,6 +241,7 @@ class DeviceSideDecoder:
         self.png_forms = bool(png_forms) and self.png  # the pipeline's png_forms == "all"
         self.webp = bool(webp)                      # the pipeline's webp == "device"
         self.webp_forms = bool(webp_forms) and self.webp  # the pipeline's webp_forms == "all"
+        self.gif = bool(gif)                        # the pipeline's gif == "device"
         self.lane_min = int(os.environ.get("DINO_SIDE_LANE_MIN", LANE_MIN_POOL))  # smaller pools: wave decoder
         self._engines: list[_SideEngine] = []
         self._rr = 0
@@ -285,7 +290,7 @@ class DeviceSideDecoder:
                             index=len(self._engines), stream_set=self.stream_set, lanes=self.lanes,
                             four_component=self.four_component, png=self.png, draft=self.draft,
                             exif_transpose=self.exif_transpose, png_forms=self.png_forms, webp=self.webp,
-                            webp_forms=self.webp_forms)
+                            webp_forms=self.webp_forms, gif=self.gif)
             self._engines.append(e)
             return e
         e = self._engines[self._rr % len(self._engines)]
@@ -357,6 +362,11 @@ class DeviceSideDecoder:
                 lossy[form[:, 0] != fallback.WEBP_DECLINED, 0] = 0
                 info, extra, _ = fallback.accept_webp_forms(info, lossy, need)
                 ws += extra
+        if self.gif:  # the GIF files, which the probe reports as any non-JPEG: their workspace was not counted
+            o = off.numpy()
+            form, need = fallback.probe_gif(hb.data_ptr() + o[:-1], np.diff(o), self.max_image_dim)
+            info, extra, _ = fallback.accept_gif(info, form, need, "device")
+            ws += extra
         if self.exif_transpose:  # the second RGB region of each image the context turns (upright sizes in info)
             o = off.numpy()
             info, extra, _ = fallback.accept_orient(info, fallback.probe_orient(hb.data_ptr() + o[:-1], np.diff(o)))

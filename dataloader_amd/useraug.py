@@ -34,7 +34,8 @@ class MI355XUserAugPipeline:
 
     def __init__(self, source: Any, spec, batch_size: int, out_dtype="bf16", device: int = 0,
                  max_image_dim: int = 0, workspace_bytes: int = 0, norm=None, resample_filter=None,
-                 png: str = "off", jpeg_draft: int = 0, exif_transpose: bool = False, webp: str = "off"):
+                 png: str = "off", jpeg_draft: int = 0, exif_transpose: bool = False, webp: str = "off",
+                 gif: str = "off"):
         self._source = source
         # EXIF orientation applied: on the context, and by Pillow for the files it does not verify
         self._exif = bool(exif_transpose)
@@ -47,6 +48,8 @@ class MI355XUserAugPipeline:
         # WebP files: the same ("host" and "device" both hand every WebP over to Pillow)
         fallback.check_webp(webp)
         self._webp = webp
+        fallback.check_gif(gif)  # (GIF files: the same)
+        self._gif = gif
         self._spec = spec
         self._batch_size = int(batch_size)
         self._out = _out_code(out_dtype)
@@ -102,6 +105,10 @@ class MI355XUserAugPipeline:
             o = offsets.numpy()
             form, need = fallback.probe_webp(host_buf.data_ptr() + o[:-1], np.diff(o), self._max_image_dim)
             info, _, _ = fallback.accept_webp(info, form, need, "host")
+        if self._gif != "off":  # and every GIF
+            o = offsets.numpy()
+            form, need = fallback.probe_gif(host_buf.data_ptr() + o[:-1], np.diff(o), self._max_image_dim)
+            info, _, _ = fallback.accept_gif(info, form, need, "host")
         if np.isin(info[:, 0], (fallback.IMG_UNSUPPORTED, fallback.IMG_LIMIT)).any() or \
                 (png != "off" and fallback.png_mask(info).any()):
             jpegs, n, rm = fallback.hand_over(list(jpegs), info[:, 0], kind=info[:, 3], png=png, draft=self._draft,

@@ -60,7 +60,8 @@
  *    dino_probe_png_forms and dino_debug_png_forms_decode; dino_ctx_set_webp (lossless WebP
  *    decoded on the device, off by default), dino_probe_webp and dino_debug_webp_decode;
  *    dino_ctx_set_webp_forms (lossy WebP decoded on the device, off by default),
- *    dino_probe_webp_forms and dino_debug_vp8_decode.
+ *    dino_probe_webp_forms and dino_debug_vp8_decode; dino_ctx_set_gif (GIF decoded on the
+ *    device, off by default), dino_probe_gif and dino_debug_gif_decode.
  */
 #ifndef DINO_INGEST_H
 #define DINO_INGEST_H
@@ -474,6 +475,38 @@ int dino_probe_webp_forms(const uint64_t* ptrs, const int64_t* lens, int32_t bat
  * DINO_IMG_NO_SPACE).  layout = {chunk bytes, frame record + coefficients, macroblock records,
  * Y / U / V planes, RGB region}. */
 int dino_debug_vp8_decode(const uint8_t* bytes, int64_t len, int32_t max_image_dim, uint8_t* rgb, int64_t rgb_cap,
+                          int32_t* info, int64_t* layout);
+
+/* GIF on this ctx, from the next call on: 0 (default) leaves every GIF file DINO_IMG_CORRUPT, as
+ * any non-JPEG; non-zero decodes frame 0 of the files whose header the device verifies inside the
+ * first 4096 bytes, bit for bit as Pillow 12's Image.open(..).convert("RGB"): GIF87a / GIF89a, a
+ * global or local colour table (the local one wins; indices past a short table are black), only
+ * extension blocks before the first image descriptor, which covers exactly the logical screen,
+ * LZW minimum code size 2..8, interlaced or not; transparency is ignored, later frames are not
+ * read.  Every other GIF (no colour table or the gray ramp 0, 1, 2, .., which Pillow opens as "L";
+ * a frame that is not the screen; another code size; an "XMP Data" application extension; a side
+ * above max_image_dim: DINO_IMG_LIMIT) reports DINO_IMG_UNSUPPORTED: the caller hands it to
+ * Pillow.  A logical screen with a zero side, and an LZW stream that ends (end code, terminator,
+ * or a sub-block the file cuts short, whose bytes are not read) before width x height pixels or
+ * holds a code above the next table entry, are DINO_IMG_CORRUPT: Pillow raises on them.
+ * The kernels are timed under dino_kernel_times id 23 ("k_png"). */
+int dino_ctx_set_gif(dino_ctx* ctx, int32_t on);
+
+/* Which files such a ctx decodes (no GPU involved; the probes have no ctx and keep reporting
+ * status -1, kind -1 for a GIF): form[i] = 0 not a GIF or one with a zero side, 1 a GIF the ctx does not decode (Pillow
+ * decides it), 2 a GIF it decodes, with wh[2 i], wh[2 i + 1] = width, height and ws_need[i] = the
+ * exact decode-workspace bytes of image i (0 unless form is 2).  The caller adds ws_need and the
+ * views' scratch (dino_augment_need) to the probe's numbers before dino_reserve.
+ * ptrs: absolute host addresses. */
+int dino_probe_gif(const uint64_t* ptrs, const int64_t* lens, int32_t batch, int32_t max_image_dim, uint8_t* form,
+                   int32_t* wh, int64_t* ws_need);
+
+/* Debug: the host model of that decode (the text the kernels compile, the 64 lanes as a loop).
+ * info = {status, width, height, form, LZW minimum code size, interlace flag, colour-table
+ * entries, 0}; status is DINO_IMG_CORRUPT and the rest 0 unless dino_probe_gif says 2; rgb
+ * receives 3 w h bytes when status is 0 (rgb_cap too small: DINO_IMG_NO_SPACE).  layout = {chunk
+ * bytes, joined LZW stream, index plane, colour table, RGB region}. */
+int dino_debug_gif_decode(const uint8_t* bytes, int64_t len, int32_t max_image_dim, uint8_t* rgb, int64_t rgb_cap,
                           int32_t* info, int64_t* layout);
 
 /* Reduced-size JPEG decode on this ctx, from the next call on: n = 0 (default) decodes every
